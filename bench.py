@@ -14,6 +14,12 @@ at N > 1 the per-GPU Jacobian partials are all-gathered over RCCL and summed on 
 Launch: `python bench.py --gpus 1` or under torch.distributed.run with --gpus N (one rank per GPU, weak
 scaling: every rank verifies its own 1M-share batch; no data-path collective).
 Prints ONE JSON line on rank 0.
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline needs: inputs, warmup, the N timed steps of
+the headline path (`--headline`, by default the batched verify with `--tpke-pipeline` batches in flight) and the line.
+`--full` adds every other leg: the exact path, the one-batch-at-a-time batched run, the Byzantine patterns, CommonCoin,
+MSM, epoch replay, ECDSA, DKG, RBC, the mcl latencies and the CPU baselines.
+`--dump-outputs DIR` writes what the headline path returned in its last timed step (the accept byte per share, as
+float32) to DIR/accept.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -99,6 +105,36 @@ def source_hash():
 
 def cpu_threads():
     return max(1, min(16, os.cpu_count() or 1))   # the GPU box's CPU share is 16 threads
+
+
+LAST_OUTPUTS = {}               # per TPKE path ("batched", "exact"): the arrays its last timed step returned
+DUMP_MAX_BYTES = 60_000_000     # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per array; if they exceed DUMP_MAX_BYTES together, a fixed seeded
+    sample of each array's elements (ascending positions, every array's share proportional to its size)."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(4 * a.size for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            keep = int(a.size * (DUMP_MAX_BYTES / total))
+            idx = np.sort(np.random.default_rng(SEED).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def plain_run(args):
+    """Without --full: only the headline's TPKE path is set up, warmed up and timed; every other leg is switched off
+    whatever its own option says."""
+    if args.headline == "batched" and args.tpke_batched:
+        args.tpke_exact = 0
+    else:
+        args.tpke_batched = 0
+    args.pattern_steps = args.mcl_reps = args.dkg_n = args.rs_n = 0
+    args.ecdsa_sigs = args.replay_n = args.ts_rounds = 0
+    args.msm_sizes = ""
+    args.no_cpu_baseline = True
 
 
 class Drbg:
@@ -1583,7 +1619,9 @@ def run_tpke_batched(args, nat, torch, dev, world, inp, d_acc, dd, n, n_cts, n_d
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    mism += int(np.sum(d_acc.cpu().numpy() != inp["expect"]))
+    got = d_acc.cpu().numpy()
+    LAST_OUTPUTS["batched"] = {"accept": got}
+    mism += int(np.sum(got != inp["expect"]))
     pool.shutdown()
     levels, ms = [], [0.0] * 6
     for p in parts:
@@ -1708,6 +1746,7 @@ def run_tpke_pipelined(args, nat, torch, dev, world, inp, dd, n, n_cts, n_dec, P
     pool.shutdown()
     expect_dev = torch.from_numpy(np.ascontiguousarray(inp["expect"]).astype(np.uint8)).to(dev)
     mism += int((slots[:args.steps] != expect_dev.unsqueeze(0)).sum().item())
+    LAST_OUTPUTS["batched"] = {"accept": slots[max(1, args.steps) - 1].cpu().numpy()}
     del slots
     levels = []
     for ln in lanes:
@@ -1805,6 +1844,7 @@ def compact_line(full):
         sb = tb["single_batch"]
         line["tpke_single_batch"] = {k: _r(sb.get(k)) for k in ("value", "ms_per_step", "decision_mismatches",
                                                                 "roofline_frac")}
+    if tb.get("pipeline"):                    # a plain run has no single_batch record, the in-flight figures it has
         line["config"]["batches_in_flight"] = tb.get("pipeline")
         line["config"]["single_batch_latency_ms"] = _r(tb.get("single_batch_ms"))
     for k in ("hw_queues", "hw_queues_env"):
@@ -1876,6 +1916,13 @@ def main():
                     help="timed TPKE steps (batches); 12 by default so that the default four batches in flight each run "
                          "three (at 3 steps one of the four contexts idles and the line under-reports the pipeline)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (exact path, one batch at a time, Byzantine patterns, "
+                         "CommonCoin, MSM, epoch replay, ECDSA, DKG, RBC, mcl latencies, CPU baselines); without it "
+                         "only the headline path is timed and the options of the other legs have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the headline path's last-step outputs (rank 0) as float32 "
+                         "DIR/<name>.npy")
     ap.add_argument("--shares", type=int, default=1048576)
     ap.add_argument("--n", type=int, default=22)
     ap.add_argument("--f", type=int, default=7)
@@ -1941,6 +1988,8 @@ def main():
     ap.add_argument("--rs-bytes", type=int, default=1 << 24)
     ap.add_argument("--mcl-reps", type=int, default=30, help="per-call latency samples of the mcl surface (0 = skip)")
     args = ap.parse_args()
+    if not args.full:
+        plain_run(args)
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -2045,6 +2094,7 @@ def main():
             raise RuntimeError(nat.last_error())
         miller_ms, fexp_ms = float(kms[0]), float(kms[1])
         got = d_acc.cpu().numpy()
+        LAST_OUTPUTS["exact"] = {"accept": got}
         mismatches += int(np.sum(got != inp["expect"]))
         t = shard.max_time_sum(dist, torch, dev, elapsed, mismatches, n)
         elapsed = t[0]
@@ -2066,17 +2116,22 @@ def main():
                           "k_final_exp_check": n * C["C_FE"] * MAC_PER_FPMUL / (fexp_ms * 1e-3) / PEAK_MAC32}})
     batched = None
     if args.tpke_batched:
-        progress("TPKE batched verify")
-        batched = run_tpke_batched(args, nat, torch, dev, world, inp, d_acc, (d_ct, d_dec, d_ui), n, n_cts, n_dec, sh)
-        if args.tpke_pipeline > 1 and args.tpke_streams <= 1:
-            # batches in flight: the headline is the pipelined rate; the one-batch-at-a-time rate stays in the record
+        pipelined = args.tpke_pipeline > 1 and args.tpke_streams <= 1
+        if args.full or not pipelined:
+            progress("TPKE batched verify")
+            batched = run_tpke_batched(args, nat, torch, dev, world, inp, d_acc, (d_ct, d_dec, d_ui), n, n_cts, n_dec,
+                                       sh)
+        if pipelined:
+            # batches in flight: the headline is the pipelined rate; with --full the one-batch-at-a-time rate is
+            # measured before it and stays in the record
             progress(f"TPKE batched verify, {args.tpke_pipeline} batches in flight")
             piped = run_tpke_pipelined(args, nat, torch, dev, world, inp, (d_ct, d_dec, d_ui), n, n_cts, n_dec,
                                        args.tpke_pipeline)
-            piped["single_batch"] = {k: batched[k] for k in ("value", "ms_per_step", "decision_mismatches", "levels")
-                                     if k in batched}
-            piped["single_batch"]["roofline_frac"] = batched["roofline"]["frac"]
-            piped["device_ms"] = batched.get("device_ms")
+            if batched is not None:
+                piped["single_batch"] = {k: batched[k] for k in ("value", "ms_per_step", "decision_mismatches",
+                                                                 "levels") if k in batched}
+                piped["single_batch"]["roofline_frac"] = batched["roofline"]["frac"]
+                piped["device_ms"] = batched.get("device_ms")
             batched = piped
     byz = None
     if args.pattern_steps > 0:
@@ -2085,6 +2140,8 @@ def main():
     head = batched if (args.headline == "batched" and batched) else exact
     if head is None:
         raise SystemExit("nothing to report: --tpke-exact 0 and --tpke-batched 0")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, LAST_OUTPUTS["batched" if head is batched else "exact"])
     msm = ts = replay = ecdsa = dkg = rs = mcl_lat = None
     if args.mcl_reps > 0 and world == 1:
         progress("mcl latency")

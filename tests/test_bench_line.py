@@ -59,6 +59,40 @@ def test_oversized_summary_is_dropped():
     assert line["roofline"]["frac"] > 0 and line["cpu_baseline"]["value"] > 0
 
 
+def test_dump_outputs_float32_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 files of the arrays as they are; beyond the size limit the same seeded sample of
+    each array (ascending positions) on every call, within the limit in all"""
+    import numpy as np
+    acc = (np.arange(1000) % 7 != 0).astype(np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), {"accept": acc})
+    got = np.load(tmp_path / "a" / "accept.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, acc.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1600)
+    other = np.arange(3000, dtype=np.uint8).reshape(30, 100)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"accept": acc, "other": other})
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in ("accept", "other")}
+    c = {k: np.load(tmp_path / "c" / f"{k}.npy") for k in ("accept", "other")}
+    assert all(np.array_equal(b[k], c[k]) and b[k].dtype == np.float32 for k in b)
+    assert len(b["accept"]) == 100 and len(b["other"]) == 300
+    assert sum(v.nbytes for v in b.values()) <= 1600
+    idx = np.sort(np.random.default_rng(bench.SEED).choice(1000, size=100, replace=False))
+    assert np.array_equal(b["accept"], acc[idx].astype(np.float32))
+
+
+def test_plain_run_keeps_only_the_headline_path():
+    import argparse
+    legs = dict(tpke_batched=1, tpke_exact=1, pattern_steps=2, mcl_reps=30, dkg_n=256, rs_n=256, ecdsa_sigs=1 << 20,
+                replay_n=256, ts_rounds=65536, msm_sizes="1048576", no_cpu_baseline=False)
+    a = argparse.Namespace(headline="batched", **legs)
+    bench.plain_run(a)
+    assert a.tpke_batched == 1 and a.tpke_exact == 0 and a.no_cpu_baseline and a.msm_sizes == ""
+    assert not any((a.pattern_steps, a.mcl_reps, a.dkg_n, a.rs_n, a.ecdsa_sigs, a.replay_n, a.ts_rounds))
+    a = argparse.Namespace(headline="exact", **legs)
+    bench.plain_run(a)
+    assert a.tpke_batched == 0 and a.tpke_exact == 1
+
+
 def test_round4_driver_run_line_is_its_detail_compacted():
     """the final round-4 driver-command run (profiles/r04/final/bench_full.txt): its last stdout line is exactly
     compact_line() of the BENCH_DETAIL record printed above it, within the size limit, with the step's HBM traffic

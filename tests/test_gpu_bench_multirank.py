@@ -33,7 +33,7 @@ def test_bench_world_size_two():
            "--gpus", "2", "--steps", "1", "--warmup", "1", "--shares", "8800", "--pattern-steps", "1",
            "--patterns", "f_validators_wrong", "--ts-rounds", "64", "--ts-n", "16", "--replay-n", "16",
            "--ecdsa-sigs", "4096", "--ecdsa-validators", "16", "--msm-sizes", "8192", "--msm-steps", "1",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=420)
     if r.returncode != 0 and os.path.isdir(os.path.join(ROOT, "gpurun_out")):
         with open(os.path.join(ROOT, "gpurun_out", "bench_multirank_failure.txt"), "w") as fh:
