@@ -539,6 +539,55 @@ int lcb_root_header_verify_dev(uint8_t *accept, const uint8_t *headers, uint64_t
                                size_t sig_len, const int32_t *key_idx, size_t n, const lcb_ecdsa_keyset *ks,
                                int use_new_chain_id, int32_t chain_id, void *stream);
 
+/* ------------------------------------------------------------------ secp256k1 public-key recovery (transaction senders)
+   The reference authenticates every transaction by recovery: TransactionVerifier.VerifyTransactions
+   (TransactionVerifier.cs:72-91) queues a block's receipts and its worker runs, per receipt,
+     receipt.RecoverPublicKey -> DefaultCrypto.RecoverSignatureHashed -> ComputeAddress -> compare with Transaction.From
+   (TransactionVerifier.cs:124-130; CryptoUtils.cs:53-58; DefaultCrypto.cs:146-168,197-200); the VM's ecrecover handlers
+   (ExternalHandler.cs:1197,1225,1242) call the same and SpecialRecoverSignatureHashed (DefaultCrypto.cs:170-195).
+   Per item: 32-byte hash, signature r || s || v at stride sig_len.  An item recovers when sig_len is 65 (old chain id)
+   or 66 (new) as use_new_chain_id says, recId = (v - 36) / 2 / chain_id (truncating; chain id 0 fails) lies in [0, 3],
+   r and s lie in [1, n), r + n < p when recId & 2, x(R) is on the curve and Q = r^-1 (s R - z G) is not infinity
+   (libsecp256k1's secp256k1_ecdsa_recover; there is NO low-s rule on recovery).  Where the reference throws, ok[i] = 0
+   and the item's output bytes are zero; nothing fails the call.  pub33_out (33 B compressed key per item) and
+   addr20_out (Keccak-256(x || y)[12:], 20 B per item) may each be null. */
+int lcb_ecdsa_recover_hashed_batch(uint8_t *pub33_out, uint8_t *addr20_out, uint8_t *ok, const uint8_t *hashes,
+                                   const uint8_t *sigs, size_t sig_len, size_t n, int use_new_chain_id,
+                                   int32_t chain_id);
+/* SpecialRecoverSignatureHashed: 65-byte signatures with v = 27 (recId 0) or 28 (recId 1), no chain id */
+int lcb_ecdsa_special_recover_hashed_batch(uint8_t *pub33_out, uint8_t *addr20_out, uint8_t *ok, const uint8_t *hashes,
+                                           const uint8_t *sigs, size_t sig_len, size_t n);
+/* The cache-miss branch of TransactionVerifier.VerifyTransactionImmediately (TransactionVerifier.cs:124-130):
+   accept[i] = the signature recovers and the recovered address equals from20[i].  The receipt.Hash == FullHash check
+   (line 115) stays with the caller.  The reference's cached-key branch is VerifySignatureHashed
+   (lcb_ecdsa_verify_hashed_batch), which enforces low s; this branch does not, exactly as in the reference. */
+int lcb_tx_verify_batch(uint8_t *accept, const uint8_t *hashes, const uint8_t *sigs, size_t sig_len,
+                        const uint8_t *from20, size_t n, int use_new_chain_id, int32_t chain_id);
+/* device-pointer forms on a stream (asynchronous), with and without an explicit context */
+int lcb_ctx_ecdsa_recover_hashed_dev(lcb_ctx *ctx, uint8_t *pub33_out, uint8_t *addr20_out, uint8_t *ok,
+                                     const uint8_t *hashes, const uint8_t *sigs, size_t sig_len, size_t n,
+                                     int use_new_chain_id, int32_t chain_id, void *stream);
+int lcb_ctx_ecdsa_special_recover_hashed_dev(lcb_ctx *ctx, uint8_t *pub33_out, uint8_t *addr20_out, uint8_t *ok,
+                                             const uint8_t *hashes, const uint8_t *sigs, size_t sig_len, size_t n,
+                                             void *stream);
+int lcb_ctx_tx_verify_dev(lcb_ctx *ctx, uint8_t *accept, const uint8_t *hashes, const uint8_t *sigs, size_t sig_len,
+                          const uint8_t *from20, size_t n, int use_new_chain_id, int32_t chain_id, void *stream);
+int lcb_ecdsa_recover_hashed_dev(uint8_t *pub33_out, uint8_t *addr20_out, uint8_t *ok, const uint8_t *hashes,
+                                 const uint8_t *sigs, size_t sig_len, size_t n, int use_new_chain_id, int32_t chain_id,
+                                 void *stream);
+int lcb_ecdsa_special_recover_hashed_dev(uint8_t *pub33_out, uint8_t *addr20_out, uint8_t *ok, const uint8_t *hashes,
+                                         const uint8_t *sigs, size_t sig_len, size_t n, void *stream);
+int lcb_tx_verify_dev(uint8_t *accept, const uint8_t *hashes, const uint8_t *sigs, size_t sig_len, const uint8_t *from20,
+                      size_t n, int use_new_chain_id, int32_t chain_id, void *stream);
+/* kernel milliseconds of the last recovery in the context: scalars, recovery, finish */
+int lcb_ctx_ecdsa_recover_phase_ms(lcb_ctx *ctx, float ms[3]);
+int lcb_ecdsa_recover_phase_ms(float ms[3]);
+/* Keccak-256 (original 0x01 padding: KeccakBytes, the RawHash of a transaction's RLP for RecoverSignature,
+   DefaultCrypto.cs:139-144) of n messages: message i is data[off[i] .. off[i + 1]); off has n + 1 entries */
+int lcb_keccak256_batch(uint8_t *out32, const uint8_t *data, const uint64_t *off, size_t n);
+int lcb_ctx_keccak256_dev(lcb_ctx *ctx, uint8_t *out32, const uint8_t *data, const uint64_t *off, size_t n, void *stream);
+int lcb_keccak256_dev(uint8_t *out32, const uint8_t *data, const uint64_t *off, size_t n, void *stream);
+
 /* ------------------------------------------------------------------ aggregation queue (one share per call)
    The consensus code verifies one share per call from many protocol threads (HoneyBadger.cs:156-158,211-212,
    ThresholdSigner.cs:62, AbstractProtocol.cs:46-47).  A queue aggregates such calls into GPU batches: submit

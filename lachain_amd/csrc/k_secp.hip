@@ -14,15 +14,10 @@
 //   k_secp_header_hash HashUtils.Keccak(BlockHeader): Keccak-256 of the RLP list, plus the Index == era check
 //   k_secp_scalars     signature parsing / recId / low-s checks, s^-1, u1 = z/s, u2 = r/s -> signed digits (job records)
 //   k_secp_verify      sum of the table entries, then x(R) mod n == r on Jacobian coordinates (no inversion)
-#include "secp.hpp"
+#include "secp_comb.hpp"             // launch shape, comb geometry, recode, comb_add_entry, secp_rec_id
 #ifndef SECP_HOST_EMULATION
 #include "gate.hpp"
 #endif
-
-#define SECP_BLOCK 256
-#define SECP_WIN 33                  // signed 8-bit digits of a scalar < n: 32 bytes + the final carry
-#define SECP_TAB 128                 // multiples 1..128 per window
-#define SECP_BATCH 16                // signatures per thread in the batched inversion
 
 struct secp_job {                    // 112 B, written by k_secp_scalars, read by k_secp_verify
     int8_t d1[36], d2[36];           // digits of u1 (generator) and u2 (key), windows 0..32
@@ -184,14 +179,8 @@ __device__ __forceinline__ void load_sig(sig_in &q, size_t i, const uint8_t *has
 #pragma unroll
         for (int k = 0; k < 8; k++) { u64 d = (u64)q.z[k] - SECP_N[k] - br; q.z[k] = (u32)d; br = (u32)(d >> 32) & 1; }
     }
-    // RestoreEncodedRecIdFromSignatureBuffer (DefaultCrypto.cs:31-44) and recId = (enc - 36) / 2 / chainId in
-    // [0, 3]; C and C# both truncate toward zero; chain id 0 is a DivideByZeroException (not verified)
-    int enc = sig_len == 66 ? (int)sg[64] * 256 + (int)sg[65] : (int)sg[64];
-    bool rec_ok = false;
-    if (chain_id != 0) {
-        int rec = (enc - 36) / 2 / chain_id;
-        rec_ok = rec >= 0 && rec <= 3;
-    }
+    // recId in [0, 3] (secp_comb.hpp); chain id 0 is a DivideByZeroException (not verified)
+    bool rec_ok = secp_rec_id(sg, sig_len, chain_id) >= 0;
     int32_t k = key_idx[i];
     bool key_in = k >= 0 && (u32)k < n_keys;
     q.key = key_in ? (u32)k : 0u;
@@ -201,18 +190,6 @@ __device__ __forceinline__ void load_sig(sig_in &q, size_t i, const uint8_t *has
     ok = ok && !u256_is_zero(q.r) && !u256_is_zero(q.s);
     if (pre_ok) ok = ok && pre_ok[i] != 0;
     q.ok = ok;
-}
-__device__ __forceinline__ void recode(int8_t *d, const sc &u) {
-    u32 carry = 0;
-#pragma unroll
-    for (int w = 0; w < 32; w++) {
-        u32 v = ((u.v[w >> 2] >> (8 * (w & 3))) & 0xffu) + carry;
-        carry = v >= 128u;                                 // digits in [-128, 127]: int8 range
-        d[w] = (int8_t)(int)(carry ? (int)v - 256 : (int)v);
-    }
-    d[32] = (int8_t)carry;
-#pragma unroll
-    for (int w = 33; w < 36; w++) d[w] = 0;
 }
 extern "C" __global__ void __launch_bounds__(SECP_BLOCK) k_secp_scalars(const uint8_t *hashes, const uint8_t *sigs,
                                                                        u32 sig_len, u32 want_len, int chain_id,
@@ -268,12 +245,6 @@ extern "C" __global__ void __launch_bounds__(SECP_BLOCK) k_secp_scalars(const ui
 }
 
 // ------------------------------------------------------------------------------------------------ verify
-__device__ __forceinline__ void comb_add_entry(secp_jac &acc, const secp_aff &e, int d) {
-    if (d == 0) return;
-    fe y = e.y;
-    if (d < 0) fe_neg(y, y);
-    jac_add_aff(acc, acc, e.x, y);
-}
 __device__ __forceinline__ void comb_add(secp_jac &acc, const secp_aff *tab, int w, int d) {
     if (d == 0) return;
     const secp_aff e = tab[w * SECP_TAB + (d < 0 ? -d : d) - 1];

@@ -117,6 +117,10 @@ struct lcb_ctx {
     struct lcb_ecdsa_keyset *ec_cache = nullptr;
     std::vector<uint8_t> ec_cache_keys;
     size_t ec_cache_pk_len = 0;
+    // public-key recovery (lcb_ecdsa.cpp): job records, Jacobian results, staging of the host-pointer forms
+    DevBuf er[6];
+    hipEvent_t er_ev[4] = {};         // around scalars / recovery / finish of the last recovery
+    bool er_ev_ready = false, er_ran = false;
 };
 
 // Enqueue scope: exclusive use of the context, stream ordered after the context's previous work, and the

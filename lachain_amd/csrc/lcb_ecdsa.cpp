@@ -206,6 +206,9 @@ void ecdsa_ctx_release(lcb_ctx *c) {
     c->ec_cache = nullptr;
     c->ec_cache_keys.clear();
     for (auto &b : c->ec) b.release();
+    if (c->er_ev_ready) for (auto &e : c->er_ev) (void)hipEventDestroy(e);
+    c->er_ev_ready = false;
+    for (auto &b : c->er) b.release();
 }
 }  // namespace lcb_int
 
@@ -365,4 +368,188 @@ extern "C" int lcb_ecdsa_sign_hashed_batch(uint8_t *sigs_out, uint8_t *ok, const
     hipMemcpyAsync(sigs_out, dout, L * n, hipMemcpyDeviceToHost, c->stream);
     hipMemcpyAsync(ok, dout + L * n, n, hipMemcpyDeviceToHost, c->stream);
     return sync_ok(c, "ecdsa sign") ? 0 : -1;
+}
+
+// ------------------------------------------------------------------ public-key recovery (transaction senders)
+// Reference: TransactionVerifier.VerifyTransactions (TransactionVerifier.cs:72-91) -> receipt.RecoverPublicKey ->
+// DefaultCrypto.RecoverSignatureHashed -> ComputeAddress -> compare with Transaction.From (TransactionVerifier.cs:124-130,
+// CryptoUtils.cs:53-58, DefaultCrypto.cs:146-168,197-200); ecrecover in the VM (ExternalHandler.cs:1197,1225,1242) and
+// SpecialRecoverSignatureHashed (DefaultCrypto.cs:170-195).  Kernels: k_secp_recover.hip.  No CPU fallback.
+namespace {
+// the recovery pipeline on device pointers; every output may be null; from20 / accept go together (lcb_tx_verify)
+int recover_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *pub33, uint8_t *addr20, uint8_t *ok, uint8_t *accept,
+                    const uint8_t *hashes, const uint8_t *sigs, size_t sig_len, const uint8_t *from20, size_t n,
+                    int special, int use_new_chain_id, int32_t chain_id) {
+    if (!n) return 0;
+    if (n > 0xffffffffu / 2) { set_error("ecdsa recover: batch too large"); return -1; }
+    if (sig_len == 0 || sig_len > 4096) { set_error("ecdsa recover: bad signature stride"); return -1; }
+    if (!c->er_ev_ready) {
+        for (auto &e : c->er_ev)
+            if (hipEventCreate(&e) != hipSuccess) { set_error("event creation"); return -1; }
+        c->er_ev_ready = true;
+    }
+    // DefaultCrypto.SignatureSize (DefaultCrypto.cs:26-29); SpecialRecoverSignatureHashed takes 65 bytes
+    u32 want = special ? 65u : (use_new_chain_id ? 66u : 65u);
+    if (sig_len != want) {      // the reference throws for every item: nothing recovers, and no signature byte is read
+        (void)hipEventRecord(c->er_ev[0], s);
+        if (pub33) (void)hipMemsetAsync(pub33, 0, 33 * n, s);
+        if (addr20) (void)hipMemsetAsync(addr20, 0, 20 * n, s);
+        if (ok) (void)hipMemsetAsync(ok, 0, n, s);
+        if (accept) (void)hipMemsetAsync(accept, 0, n, s);
+        for (int k = 1; k < 4; k++) (void)hipEventRecord(c->er_ev[k], s);
+        c->er_ran = true;
+        return launch_ok("ecdsa recover") ? 0 : -1;
+    }
+    const void *gt = gen_table(s);
+    if (!gt) return -1;
+    void *jobs = c->er[0].get(lcbk_secp_rjob_bytes() * n), *pts = c->er[1].get(lcbk_secp_rpoint_bytes() * n);
+    if (!jobs || !pts) { set_error("device allocation failed"); return -1; }
+    (void)hipEventRecord(c->er_ev[0], s);
+    lcbk_secp_rec_scalars(s, hashes, sigs, (u32)sig_len, want, chain_id, special, (u32)n, jobs);
+    (void)hipEventRecord(c->er_ev[1], s);
+    lcbk_secp_recover(s, jobs, (u32)n, gt, pts);
+    (void)hipEventRecord(c->er_ev[2], s);
+    lcbk_secp_rec_finish(s, pts, (u32)n, pub33, addr20, ok, from20, accept);
+    (void)hipEventRecord(c->er_ev[3], s);
+    c->er_ran = true;
+    return launch_ok("ecdsa recover launch") ? 0 : -1;
+}
+
+int recover_host(uint8_t *pub33, uint8_t *addr20, uint8_t *ok, uint8_t *accept, const uint8_t *hashes,
+                 const uint8_t *sigs, size_t sig_len, const uint8_t *from20, size_t n, int special, int use_new_chain_id,
+                 int32_t chain_id) {
+    lcb_ctx *c = ctx_sync();
+    if (!c) return -1;
+    if (!n) return 0;
+    if (sig_len == 0 || sig_len > 4096) { set_error("ecdsa recover: bad signature stride"); return -1; }
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    Enq q(c, c->stream);
+    hipStream_t s = c->stream;
+    uint8_t *dh = (uint8_t *)c->er[2].get(32 * n), *dsig = (uint8_t *)c->er[3].get(sig_len * n);
+    uint8_t *dfrom = from20 ? (uint8_t *)c->er[4].get(20 * n) : nullptr;
+    uint8_t *dout = (uint8_t *)c->er[5].get(55 * n);        // 33 key | 20 address | ok | accept
+    if (!dh || !dsig || (from20 && !dfrom) || !dout) { set_error("device allocation failed"); return -1; }
+    uint8_t *dpub = dout, *daddr = dout + 33 * n, *dok = dout + 53 * n, *dacc = dout + 54 * n;
+    hipMemcpyAsync(dh, hashes, 32 * n, hipMemcpyHostToDevice, s);
+    hipMemcpyAsync(dsig, sigs, sig_len * n, hipMemcpyHostToDevice, s);
+    if (from20) hipMemcpyAsync(dfrom, from20, 20 * n, hipMemcpyHostToDevice, s);
+    if (recover_enqueue(c, s, pub33 ? dpub : nullptr, addr20 ? daddr : nullptr, ok ? dok : nullptr,
+                        accept ? dacc : nullptr, dh, dsig, sig_len, dfrom, n, special, use_new_chain_id, chain_id))
+        return -1;
+    if (pub33) hipMemcpyAsync(pub33, dpub, 33 * n, hipMemcpyDeviceToHost, s);
+    if (addr20) hipMemcpyAsync(addr20, daddr, 20 * n, hipMemcpyDeviceToHost, s);
+    if (ok) hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, s);
+    if (accept) hipMemcpyAsync(accept, dacc, n, hipMemcpyDeviceToHost, s);
+    return sync_ok(c, "ecdsa recover") ? 0 : -1;
+}
+}  // namespace
+
+extern "C" int lcb_ctx_ecdsa_recover_hashed_dev(lcb_ctx *ctx, uint8_t *pub33_out, uint8_t *addr20_out, uint8_t *ok,
+                                                const uint8_t *hashes, const uint8_t *sigs, size_t sig_len, size_t n,
+                                                int use_new_chain_id, int32_t chain_id, void *stream) {
+    lcb_ctx *c = ctx_resolve(ctx);
+    if (!c) return -1;
+    Enq q(c, (hipStream_t)stream);
+    return recover_enqueue(c, q.s, pub33_out, addr20_out, ok, nullptr, hashes, sigs, sig_len, nullptr, n, 0,
+                           use_new_chain_id, chain_id);
+}
+extern "C" int lcb_ctx_ecdsa_special_recover_hashed_dev(lcb_ctx *ctx, uint8_t *pub33_out, uint8_t *addr20_out,
+                                                        uint8_t *ok, const uint8_t *hashes, const uint8_t *sigs,
+                                                        size_t sig_len, size_t n, void *stream) {
+    lcb_ctx *c = ctx_resolve(ctx);
+    if (!c) return -1;
+    Enq q(c, (hipStream_t)stream);
+    return recover_enqueue(c, q.s, pub33_out, addr20_out, ok, nullptr, hashes, sigs, sig_len, nullptr, n, 1, 0, 0);
+}
+extern "C" int lcb_ctx_tx_verify_dev(lcb_ctx *ctx, uint8_t *accept, const uint8_t *hashes, const uint8_t *sigs,
+                                     size_t sig_len, const uint8_t *from20, size_t n, int use_new_chain_id,
+                                     int32_t chain_id, void *stream) {
+    lcb_ctx *c = ctx_resolve(ctx);
+    if (!c) return -1;
+    if (n && (!accept || !from20)) { set_error("tx verify: accept and from20 are required"); return -1; }
+    Enq q(c, (hipStream_t)stream);
+    return recover_enqueue(c, q.s, nullptr, nullptr, nullptr, accept, hashes, sigs, sig_len, from20, n, 0,
+                           use_new_chain_id, chain_id);
+}
+extern "C" int lcb_ecdsa_recover_hashed_dev(uint8_t *pub33_out, uint8_t *addr20_out, uint8_t *ok, const uint8_t *hashes,
+                                            const uint8_t *sigs, size_t sig_len, size_t n, int use_new_chain_id,
+                                            int32_t chain_id, void *stream) {
+    return lcb_ctx_ecdsa_recover_hashed_dev(nullptr, pub33_out, addr20_out, ok, hashes, sigs, sig_len, n,
+                                            use_new_chain_id, chain_id, stream);
+}
+extern "C" int lcb_ecdsa_special_recover_hashed_dev(uint8_t *pub33_out, uint8_t *addr20_out, uint8_t *ok,
+                                                    const uint8_t *hashes, const uint8_t *sigs, size_t sig_len, size_t n,
+                                                    void *stream) {
+    return lcb_ctx_ecdsa_special_recover_hashed_dev(nullptr, pub33_out, addr20_out, ok, hashes, sigs, sig_len, n, stream);
+}
+extern "C" int lcb_tx_verify_dev(uint8_t *accept, const uint8_t *hashes, const uint8_t *sigs, size_t sig_len,
+                                 const uint8_t *from20, size_t n, int use_new_chain_id, int32_t chain_id, void *stream) {
+    return lcb_ctx_tx_verify_dev(nullptr, accept, hashes, sigs, sig_len, from20, n, use_new_chain_id, chain_id, stream);
+}
+extern "C" int lcb_ecdsa_recover_hashed_batch(uint8_t *pub33_out, uint8_t *addr20_out, uint8_t *ok,
+                                              const uint8_t *hashes, const uint8_t *sigs, size_t sig_len, size_t n,
+                                              int use_new_chain_id, int32_t chain_id) {
+    return recover_host(pub33_out, addr20_out, ok, nullptr, hashes, sigs, sig_len, nullptr, n, 0, use_new_chain_id,
+                        chain_id);
+}
+extern "C" int lcb_ecdsa_special_recover_hashed_batch(uint8_t *pub33_out, uint8_t *addr20_out, uint8_t *ok,
+                                                      const uint8_t *hashes, const uint8_t *sigs, size_t sig_len,
+                                                      size_t n) {
+    return recover_host(pub33_out, addr20_out, ok, nullptr, hashes, sigs, sig_len, nullptr, n, 1, 0, 0);
+}
+extern "C" int lcb_tx_verify_batch(uint8_t *accept, const uint8_t *hashes, const uint8_t *sigs, size_t sig_len,
+                                   const uint8_t *from20, size_t n, int use_new_chain_id, int32_t chain_id) {
+    if (n && (!accept || !from20)) { set_error("tx verify: accept and from20 are required"); return -1; }
+    return recover_host(nullptr, nullptr, nullptr, accept, hashes, sigs, sig_len, from20, n, 0, use_new_chain_id,
+                        chain_id);
+}
+// kernel milliseconds of the context's last recovery: scalars, recovery, finish
+extern "C" int lcb_ctx_ecdsa_recover_phase_ms(lcb_ctx *ctx, float ms[3]) {
+    lcb_ctx *c = ctx_resolve(ctx);
+    if (!c) return -1;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    if (!c->er_ran) { set_error("no ECDSA recovery has run in this context"); return -1; }
+    for (int k = 0; k < 3; k++) {
+        hipError_t e = hipEventSynchronize(c->er_ev[k + 1]);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[k], c->er_ev[k], c->er_ev[k + 1]);
+        if (e != hipSuccess) { set_error("ecdsa recover phase timing", e); return -1; }
+    }
+    return 0;
+}
+extern "C" int lcb_ecdsa_recover_phase_ms(float ms[3]) { return lcb_ctx_ecdsa_recover_phase_ms(nullptr, ms); }
+
+// Keccak-256 of variable-length messages (KeccakBytes; the RawHash of RecoverSignature, DefaultCrypto.cs:139-144).
+// off[n] bounds the data: the device form trusts the caller's offsets, the host form checks them.
+extern "C" int lcb_ctx_keccak256_dev(lcb_ctx *ctx, uint8_t *out32, const uint8_t *data, const uint64_t *off, size_t n,
+                                     void *stream) {
+    lcb_ctx *c = ctx_resolve(ctx);
+    if (!c) return -1;
+    Enq q(c, (hipStream_t)stream);
+    if (!n) return 0;
+    if (n > 0xffffffffu / 2) { set_error("keccak256: batch too large"); return -1; }
+    lcbk_keccak256(q.s, data, off, (u32)n, out32);
+    return launch_ok("keccak256 launch") ? 0 : -1;
+}
+extern "C" int lcb_keccak256_dev(uint8_t *out32, const uint8_t *data, const uint64_t *off, size_t n, void *stream) {
+    return lcb_ctx_keccak256_dev(nullptr, out32, data, off, n, stream);
+}
+extern "C" int lcb_keccak256_batch(uint8_t *out32, const uint8_t *data, const uint64_t *off, size_t n) {
+    lcb_ctx *c = ctx_sync();
+    if (!c) return -1;
+    if (!n) return 0;
+    for (size_t i = 0; i < n; i++)
+        if (off[i + 1] < off[i]) { set_error("keccak256: offsets must not decrease"); return -1; }
+    size_t bytes = (size_t)(off[n] - off[0]);
+    std::vector<uint64_t> rel(n + 1);
+    for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
+    Enq q(c, c->stream);
+    hipStream_t s = c->stream;
+    uint8_t *dd = (uint8_t *)c->er[2].get(bytes), *dout = (uint8_t *)c->er[5].get(32 * n);
+    uint64_t *doff = (uint64_t *)c->er[3].get(8 * (n + 1));
+    if (!dd || !dout || !doff) { set_error("device allocation failed"); return -1; }
+    if (bytes) hipMemcpyAsync(dd, data + off[0], bytes, hipMemcpyHostToDevice, s);
+    hipMemcpyAsync(doff, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, s);
+    if (lcb_ctx_keccak256_dev(c, dout, dd, doff, n, s)) return -1;
+    hipMemcpyAsync(out32, dout, 32 * n, hipMemcpyDeviceToHost, s);
+    return sync_ok(c, "keccak256") ? 0 : -1;
 }

@@ -110,7 +110,11 @@ SDI fe fe_from_v(const u32x8 &v) { fe a; for (int i = 0; i < 8; i++) a.v[i] = v[
 SDI void fe_mul(fe &r, const fe &a, const fe &b) { r = fe_from_v(secp_asm_mul(fe_to_v(a), fe_to_v(b))); }
 SDI void fe_sqr(fe &r, const fe &a) { r = fe_from_v(secp_asm_sqr(fe_to_v(a))); }
 #else
+#ifndef SECP_COUNT_PRODUCT            // the host emulation may count field products (tools/emul/secp_recover_emul.cpp)
+#define SECP_COUNT_PRODUCT()
+#endif
 SDI void fe_mul(fe &r, const fe &a, const fe &b) {
+    SECP_COUNT_PRODUCT();
     u32 t[16];
 #pragma unroll
     for (int i = 0; i < 16; i++) t[i] = 0;
@@ -129,6 +133,7 @@ SDI void fe_mul(fe &r, const fe &a, const fe &b) {
 }
 SDI void fe_sqr(fe &r, const fe &a) {
     // off-diagonal products once, doubled, plus the squares
+    SECP_COUNT_PRODUCT();
     u32 t[16];
 #pragma unroll
     for (int i = 0; i < 16; i++) t[i] = 0;
@@ -292,6 +297,80 @@ SDI void sc_mont_inv(sc &r, const sc &a) {
         if ((e >> (i & 31)) & 1) sc_mont_mul(acc, acc, a);
     }
     r = acc;
+}
+
+// ------------------------------------------------------------------------------------------------ endomorphism
+// phi(x, y) = (beta x, y) = lambda (x, y), with beta^3 = 1 mod p and lambda^2 + lambda + 1 = 0 mod n (the pair for which
+// phi(G) = lambda G; lambda is the smaller of the two roots).  A scalar k < n splits as k = k1 + k2 lambda (mod n) with |k1|, |k2| < 2^128 (public-key recovery,
+// k_secp_recover.hip).  Derivation, with Python integers (tests/test_secp_recover_emul.py repeats it):
+//   extended Euclid on (n, lambda) gives rows (r_i, t_i) with r_i + (-t_i) lambda = 0 mod n; with l the last row whose
+//   r_l >= sqrt(n): (a1, b1) = (r_{l+1}, -t_{l+1}), (a2, b2) = the shorter of (r_l, -t_l) and (r_{l+2}, -t_{l+2}):
+//     a1 = b2 = 0x3086d221a7d46bcde86c90e49284eb15, -b1 = 0xe4437ed6010e88286f547fa90abfe4c3,
+//     a2 = 0x114ca50f7a8e2f3f657c1108d9d44cfd8
+//   g1 = round(2^384 b2 / n), g2 = round(2^384 (-b1) / n); c1 = round(k g1 / 2^384), c2 = round(k g2 / 2^384);
+//   k1 = k - c1 a1 - c2 a2, k2 = c1 (-b1) - c2 b2   (exact integers; computed mod 2^256 as two's complement)
+__constant__ static const u32 SECP_LAMBDA[8] = {0x1b23bd72u, 0xdf02967cu, 0x20816678u, 0x122e22eau,
+                                                0x8812645au, 0xa5261c02u, 0xc05c30e0u, 0x5363ad4cu};
+__constant__ static const u32 SECP_BETA[8] = {0x719501eeu, 0xc1396c28u, 0x12f58995u, 0x9cf04975u,
+                                              0xac3434e9u, 0x6e64479eu, 0x657c0710u, 0x7ae96a2bu};
+__constant__ static const u32 SECP_GLV_G1[8] = {0x45dbb031u, 0xe893209au, 0x71e8ca7fu, 0x3daa8a14u,
+                                                0x9284eb15u, 0xe86c90e4u, 0xa7d46bcdu, 0x3086d221u};
+__constant__ static const u32 SECP_GLV_G2[8] = {0x8ac47f71u, 0x1571b4aeu, 0x9df506c6u, 0x221208acu,
+                                                0x0abfe4c4u, 0x6f547fa9u, 0x010e8828u, 0xe4437ed6u};
+__constant__ static const u32 SECP_GLV_A1[5] = {0x9284eb15u, 0xe86c90e4u, 0xa7d46bcdu, 0x3086d221u, 0u};   // = b2
+__constant__ static const u32 SECP_GLV_MB1[5] = {0x0abfe4c3u, 0x6f547fa9u, 0x010e8828u, 0xe4437ed6u, 0u};  // -b1
+__constant__ static const u32 SECP_GLV_A2[5] = {0x9d44cfd8u, 0x57c1108du, 0xa8e2f3f6u, 0x14ca50f7u, 1u};
+// c[0..4] = round(k g / 2^384) for 256-bit k, g (at most 2^128, hence the fifth limb)
+SDI void glv_mul_shift384(u32 *c, const u32 *k, const u32 *g) {
+    u32 t[17];
+#pragma unroll
+    for (int i = 0; i < 17; i++) t[i] = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        u64 cy = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) { cy += (u64)k[j] * g[i] + t[i + j]; t[i + j] = (u32)cy; cy >>= 32; }
+        t[i + 8] = (u32)cy;
+    }
+    u64 cy = (u64)t[11] + 0x80000000u;                  // + 2^383
+    cy >>= 32;
+#pragma unroll
+    for (int i = 0; i < 5; i++) { cy += t[12 + i]; c[i] = (u32)cy; cy >>= 32; }
+}
+// r = a b mod 2^256 for 5-limb a, b
+SDI void glv_mul_lo(u32 *r, const u32 *a, const u32 *b) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) r[i] = 0;
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        u64 cy = 0;
+#pragma unroll
+        for (int j = 0; j < 5; j++)
+            if (i + j < 8) { cy += (u64)a[j] * b[i] + r[i + j]; r[i + j] = (u32)cy; cy >>= 32; }
+        if (i + 5 < 8) r[i + 5] = (u32)cy;
+    }
+}
+SDI void u256_sub(u32 *r, const u32 *a, const u32 *b) {
+    u32 br = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) { u64 d = (u64)a[i] - b[i] - br; r[i] = (u32)d; br = (u32)(d >> 32) & 1; }
+}
+// k = k1 + k2 lambda (mod n): magnitudes m1, m2 (8 limbs; below 2^128 for k < n) and signs (true: negative)
+SDI void glv_split(u32 *m1, bool &neg1, u32 *m2, bool &neg2, const u32 *k) {
+    u32 c1[5], c2[5], t[8], zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    glv_mul_shift384(c1, k, SECP_GLV_G1);
+    glv_mul_shift384(c2, k, SECP_GLV_G2);
+    glv_mul_lo(t, c1, SECP_GLV_A1);
+    u256_sub(m1, k, t);
+    glv_mul_lo(t, c2, SECP_GLV_A2);
+    u256_sub(m1, m1, t);
+    glv_mul_lo(m2, c1, SECP_GLV_MB1);
+    glv_mul_lo(t, c2, SECP_GLV_A1);
+    u256_sub(m2, m2, t);
+    neg1 = m1[7] >> 31;
+    neg2 = m2[7] >> 31;
+    if (neg1) u256_sub(m1, zero, m1);
+    if (neg2) u256_sub(m2, zero, m2);
 }
 
 // ------------------------------------------------------------------------------------------------ points

@@ -195,6 +195,21 @@ _SIGS = {
     "lcb_ecdsa_sign_hashed_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p, c_size, ctypes.c_int, ctypes.c_int32,
                                                  ctypes.c_void_p]),
+    "lcb_ecdsa_recover_hashed_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_size, c_size, ctypes.c_int,
+                                                      ctypes.c_int32]),
+    "lcb_ecdsa_special_recover_hashed_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_size, c_size]),
+    "lcb_tx_verify_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_size, c_u8p, c_size, ctypes.c_int, ctypes.c_int32]),
+    "lcb_ecdsa_recover_hashed_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, c_size, c_size, ctypes.c_int, ctypes.c_int32,
+                                                    ctypes.c_void_p]),
+    "lcb_ecdsa_special_recover_hashed_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                            ctypes.c_void_p, ctypes.c_void_p, c_size, c_size,
+                                                            ctypes.c_void_p]),
+    "lcb_tx_verify_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_size, ctypes.c_void_p,
+                                         c_size, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p]),
+    "lcb_ecdsa_recover_phase_ms": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float)]),
+    "lcb_keccak256_batch": (ctypes.c_int, [c_u8p, c_u8p, ctypes.POINTER(ctypes.c_uint64), c_size]),
+    "lcb_keccak256_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_size, ctypes.c_void_p]),
     "lcb_ctx_create": (ctypes.c_void_p, []),
     "lcb_ctx_destroy": (None, [ctypes.c_void_p]),
     "lcb_ctx_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
@@ -205,7 +220,8 @@ for _name in ("tpke_prepare_dev", "tpke_verify_prepared_dev", "tpke_verify_prepa
               "tpke_verify_phase_ms", "ts_prepare_dev", "ts_verify_prepared_dev", "ts_assemble_dev", "g1_lagrange_dev",
               "g2_lagrange_dev", "g1_msm_dev", "g1_msm_glv_dev", "g1_msm_phase_ms", "g1_jac_sum_dev", "ecdsa_verify_hashed_dev",
               "root_header_verify_dev", "ecdsa_pubkey_dev", "ecdsa_sign_hashed_dev", "ecdsa_phase_ms", "batched_census",
-              "tpke_combine_ordered_dev", "ts_assemble_ordered_dev"):
+              "tpke_combine_ordered_dev", "ts_assemble_ordered_dev", "ecdsa_recover_hashed_dev",
+              "ecdsa_special_recover_hashed_dev", "tx_verify_dev", "ecdsa_recover_phase_ms", "keccak256_dev"):
     _res, _args = _SIGS["lcb_" + _name]
     _SIGS["lcb_ctx_" + _name] = (_res, [ctypes.c_void_p] + list(_args))
 
@@ -602,6 +618,64 @@ def ecdsa_sign_hashed_batch(hashes: bytes, privs: bytes, nonces: bytes, use_new_
     _check(lib().lcb_ecdsa_sign_hashed_batch(po, pok, ph, pp, pn, n, int(bool(use_new_chain_id)), chain_id),
            "ecdsa_sign_hashed_batch")
     return bytes(ob)[: L * n], bytes(okb)[:n]
+
+
+def _recover(fn_name, hashes: bytes, sigs: bytes, sig_len: int, *tail):
+    n = len(hashes) // 32
+    keep = []
+    _, ph = _bytes_ptr_keep(keep, hashes)
+    _, ps = _bytes_ptr_keep(keep, sigs)
+    pb, pp = _out(33 * n)
+    ab, pa = _out(20 * n)
+    okb, pok = _out(n)
+    _check(getattr(lib(), fn_name)(pp, pa, pok, ph, ps, sig_len, n, *tail), fn_name)
+    return bytes(pb)[: 33 * n], bytes(ab)[: 20 * n], bytes(okb)[:n]
+
+
+def ecdsa_recover_hashed_batch(hashes: bytes, sigs: bytes, sig_len: int, use_new_chain_id: bool, chain_id: int):
+    """DefaultCrypto.RecoverSignatureHashed + ComputeAddress over a batch: (compressed keys, addresses, ok); where
+    the reference throws, ok is 0 and the item's bytes are zero"""
+    return _recover("lcb_ecdsa_recover_hashed_batch", hashes, sigs, sig_len, int(bool(use_new_chain_id)), chain_id)
+
+
+def ecdsa_special_recover_hashed_batch(hashes: bytes, sigs: bytes, sig_len: int = 65):
+    """DefaultCrypto.SpecialRecoverSignatureHashed (v = 27 / 28, no chain id): (compressed keys, addresses, ok)"""
+    return _recover("lcb_ecdsa_special_recover_hashed_batch", hashes, sigs, sig_len)
+
+
+def tx_verify_batch(hashes: bytes, sigs: bytes, sig_len: int, from20: bytes, use_new_chain_id: bool,
+                    chain_id: int) -> bytes:
+    """TransactionVerifier's cache-miss branch: one accept byte per transaction (recovers, and the address is From)"""
+    n = len(hashes) // 32
+    keep = []
+    _, ph = _bytes_ptr_keep(keep, hashes)
+    _, ps = _bytes_ptr_keep(keep, sigs)
+    _, pf = _bytes_ptr_keep(keep, from20)
+    ob, po = _out(n)
+    _check(lib().lcb_tx_verify_batch(po, ph, ps, sig_len, pf, n, int(bool(use_new_chain_id)), chain_id),
+           "tx_verify_batch")
+    return bytes(ob)[:n]
+
+
+def ecdsa_recover_phase_ms():
+    """kernel milliseconds of the calling thread's last recovery: [scalars, recovery, finish]"""
+    ms = (ctypes.c_float * 3)()
+    _check(lib().lcb_ecdsa_recover_phase_ms(ms), "ecdsa_recover_phase_ms")
+    return list(ms)
+
+
+def keccak256_batch(msgs) -> bytes:
+    """Keccak-256 (KeccakBytes) of each message: 32 bytes per message"""
+    n = len(msgs)
+    off = [0]
+    for m in msgs:
+        off.append(off[-1] + len(m))
+    keep = []
+    _, pd = _bytes_ptr_keep(keep, b"".join(msgs))
+    offs = (ctypes.c_uint64 * (n + 1))(*off)
+    ob, po = _out(32 * n)
+    _check(lib().lcb_keccak256_batch(po, pd, offs, n), "keccak256_batch")
+    return bytes(ob)[: 32 * n]
 
 
 class EcdsaKeySet:
