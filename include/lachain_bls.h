@@ -473,6 +473,62 @@ int lcb_rs_encode(uint8_t *shards_out, const uint8_t *input, size_t input_len, i
 int lcb_rs_decode(uint8_t *out, const uint8_t *echo_data, const int32_t *from, int n_echos, size_t shard_size,
                   int n_shards, int erasures);
 
+/* ------------------------------------------------------------------ reliable broadcast: Merkle layer
+   Every shard travels with a Keccak-256 Merkle proof (original padding, as lcb_keccak256_batch).  The tree of an
+   instance with n shards is a heap of 2T 32-byte nodes, T the smallest power of two >= n (ReliableBroadcast.cs:41-43,
+   375-386): tree[T + i] = Keccak(shard i), zero bytes for n <= i < T, tree[i] = Keccak(tree[2i] || tree[2i + 1]), root
+   tree[1], node 0 zero.  The proof of shard i is tree[((i + T) >> j) ^ 1], j = 0 .. depth - 1, depth = log2 T
+   (MerkleTreeBranch, :366-373).  1 <= n <= 256; f is the reference's F (2f parity shards, f = 0: none); offsets are
+   uint64 with one entry more than items, in bytes unless stated; batches are many instances of one (n, f) per call.
+   lcb_rbc_shard_size: AugmentInput's shard size ceil((payload_len + 4) / (n - 2f)) (:311-319), 0 on bad arguments;
+     lcb_rbc_tree_depth: log2 T, -1 on bad arguments.  Both are host arithmetic and need no device.
+   lcb_rbc_val_batch = HandleInputMessage's AugmentInput + ConstructValMessages (:116, :321-338) for B payloads
+     (payload b = payloads[payload_off[b] .. payload_off[b + 1])): shards_out = n * S_b bytes per instance in instance
+     order, roots_out = B x 32, proofs_out = B x n x depth x 32.  Each output may be null.
+   lcb_rbc_check_echo_* = CheckEchoMessage (:296-309) per item: accept[t] = 1 iff the walk from Keccak(data_t) at leaf
+     from[t] over the item's proof hashes proofs[proof_off[t] .. proof_off[t + 1]) (offsets in hashes) ends at the root
+     with roots[t]; a proof shorter than the depth rejects, entries beyond it are ignored, from outside [0, n) rejects.
+   lcb_rbc_merkle_tree_* = ConstructMerkleTree for shards the caller holds (instance b: n_shards equal shards in
+     shards[shard_off[b] .. shard_off[b + 1])): trees_out = B x 2T x 32 (8-byte aligned in the device forms).
+   lcb_rbc_decode_batch = TrySendReadyMessageFromEchos' work (:201-234): exactly n - 2f echoes per instance in any order
+     (instance b's echoes concatenated in echo_data[echo_off[b] .. echo_off[b + 1]), echo e of it is shard
+     from[b * (n - 2f) + e]); shards_out as lcb_rs_decode gives them, roots_out the rebuilt tree's root, root_ok[b] =
+     (status[b] and rebuilt == expected_roots[b]); expected_roots / root_ok / roots_out / shards_out may be null.  A
+     duplicate or out-of-range index or an unsolvable erasure set gives status[b] = 0 and zero output for that instance
+     alone.
+   The *_dev forms take device pointers and are asynchronous on `stream`; they trust the caller's offsets. */
+size_t lcb_rbc_shard_size(size_t payload_len, int n, int f);
+int lcb_rbc_tree_depth(int n);
+int lcb_rbc_val_batch(uint8_t *shards_out, uint8_t *roots_out, uint8_t *proofs_out, const uint8_t *payloads,
+                      const uint64_t *payload_off, size_t n_instances, int n, int f);
+int lcb_rbc_check_echo_batch(uint8_t *accept, const uint8_t *data, const uint64_t *data_off, const int32_t *from,
+                             const uint8_t *roots, const uint8_t *proofs, const uint64_t *proof_off, size_t n_items,
+                             int n_shards);
+int lcb_ctx_rbc_check_echo_dev(lcb_ctx *ctx, uint8_t *accept, const uint8_t *data, const uint64_t *data_off,
+                               const int32_t *from, const uint8_t *roots, const uint8_t *proofs,
+                               const uint64_t *proof_off, size_t n_items, int n_shards, void *stream);
+int lcb_rbc_check_echo_dev(uint8_t *accept, const uint8_t *data, const uint64_t *data_off, const int32_t *from,
+                           const uint8_t *roots, const uint8_t *proofs, const uint64_t *proof_off, size_t n_items,
+                           int n_shards, void *stream);
+int lcb_rbc_merkle_tree_batch(uint8_t *trees_out, const uint8_t *shards, const uint64_t *shard_off, size_t n_instances,
+                              int n_shards);
+int lcb_ctx_rbc_merkle_tree_dev(lcb_ctx *ctx, uint8_t *trees_out, const uint8_t *shards, const uint64_t *shard_off,
+                                size_t n_instances, int n_shards, void *stream);
+int lcb_rbc_merkle_tree_dev(uint8_t *trees_out, const uint8_t *shards, const uint64_t *shard_off, size_t n_instances,
+                            int n_shards, void *stream);
+int lcb_rbc_decode_batch(uint8_t *shards_out, uint8_t *status, uint8_t *root_ok, uint8_t *roots_out,
+                         const uint8_t *echo_data, const uint64_t *echo_off, const int32_t *from,
+                         const uint8_t *expected_roots, size_t n_instances, int n, int f);
+/* MerkleTree.ComputeRoot (MerkleTree.cs:139-191; the block's transaction root checked in BlockManager.cs:692): tree t is
+   hashes[off[t] .. off[t + 1]) (offsets in hashes).  No hash: status[t] = 0 (the reference's null) and a zero root; one
+   hash: itself; otherwise pairs level by level, an odd last node paired with itself.  The device forms also take
+   n_hashes >= off[n_trees], which sizes the context's workspace. */
+int lcb_merkle_root_batch(uint8_t *roots_out, uint8_t *status, const uint8_t *hashes, const uint64_t *off, size_t n_trees);
+int lcb_ctx_merkle_root_dev(lcb_ctx *ctx, uint8_t *roots_out, uint8_t *status, const uint8_t *hashes, const uint64_t *off,
+                            size_t n_trees, size_t n_hashes, void *stream);
+int lcb_merkle_root_dev(uint8_t *roots_out, uint8_t *status, const uint8_t *hashes, const uint64_t *off, size_t n_trees,
+                        size_t n_hashes, void *stream);
+
 /* ------------------------------------------------------------------ secp256k1 ECDSA header signatures
    RootProtocol checks every SignedHeaderMessage with
      DefaultCrypto.VerifySignatureHashed(header.Keccak(), signature, EcdsaPublicKeySet[idx].EncodeCompressed(),

@@ -77,6 +77,13 @@ extern "C" void lcbk_g1a_to_jac(dim3 grid, hipStream_t s, const void *in, u32 n,
 extern "C" const void *lcbk_rs_matrix_kernel();
 extern "C" void lcbk_rs_matrix(hipStream_t s, const int *pe, int m, const int *pk, int k, int n, uint8_t *M, uint8_t *ok);
 extern "C" void lcbk_rs_apply(hipStream_t s, const uint8_t *M, const uint8_t *ok, int m, int k, const uint8_t *src, size_t S, const int *pe, uint8_t *dst);
+extern "C" const void *lcbk_rs_matrix_batch_kernel();
+extern "C" void lcbk_rs_matrix_batch(hipStream_t s, const int *pos, int m, int k, int n, const uint8_t *valid, uint8_t *M, uint8_t *ok, unsigned B);
+extern "C" void lcbk_rs_apply_batch(hipStream_t s, const uint8_t *M, size_t M_stride, const uint8_t *ok, size_t ok_stride, int m, int k, int n, const uint8_t *src, const uint64_t *src_off, const int *pos, size_t pos_stride, uint8_t *dst, const uint64_t *dst_off, int copy, size_t max_S, unsigned B);
+extern "C" void lcbk_rbc_augment(hipStream_t s, const uint8_t *payload, const uint64_t *poff, uint8_t *shards, const uint64_t *soff, int n, int k, size_t max_bytes, unsigned B);
+extern "C" void lcbk_rbc_tree(hipStream_t s, const uint8_t *shards, const uint64_t *soff, int n, int depth, void *trees, void *roots, void *proofs, unsigned B);
+extern "C" void lcbk_rbc_echo(hipStream_t s, uint8_t *accept, const uint8_t *data, const uint64_t *doff, const int *from, const uint8_t *roots, const uint8_t *proofs, const uint64_t *poff, u32 n_items, int n);
+extern "C" void lcbk_merkle_root(hipStream_t s, uint8_t *roots, uint8_t *status, const uint8_t *hashes, const uint64_t *off, uint8_t *ws, unsigned n_trees);
 extern "C" size_t lcbk_secp_job_bytes(void);
 extern "C" size_t lcbk_secp_table_bytes(void);
 extern "C" size_t lcbk_secp_aff_bytes(void);

@@ -121,6 +121,8 @@ struct lcb_ctx {
     DevBuf er[6];
     hipEvent_t er_ev[4] = {};         // around scalars / recovery / finish of the last recovery
     bool er_ev_ready = false, er_ran = false;
+    // reliable-broadcast Merkle layer and block roots (lcb_rbc.cpp): staging, offsets, RS positions / matrices, trees
+    DevBuf rbc[12];
 };
 
 // Enqueue scope: exclusive use of the context, stream ordered after the context's previous work, and the

@@ -991,6 +991,7 @@ void ctx_free(lcb_ctx *c) {
     for (auto &b : c->out) b.release();
     for (auto &b : c->dkg) b.release();
     for (auto &b : c->mcl) b.release();
+    for (auto &b : c->rbc) b.release();
     c->pc_lines.release();
     for (auto &b : c->t_coop) b.release();
     c->cc_lines.release();

@@ -1,0 +1,329 @@
+// lachain_amd/csrc/lcb_rbc.cpp — host side of the reliable broadcast's Merkle layer and the block transaction root
+// (include/lachain_bls.h "reliable broadcast: Merkle layer").
+//
+// Reference calls: ReliableBroadcast.HandleInputMessage -> AugmentInput + ConstructValMessages (ReliableBroadcast.cs:
+// 116, 311-338), CheckEchoMessage (:173, :296-309), TrySendReadyMessageFromEchos (:201-234: DecodeFromEchos, rebuild the
+// tree, compare the root), MerkleTree.ComputeRoot (MerkleTree.cs:183-191; BlockManager.cs:692).  Each entry point is a
+// handful of launches over the whole batch (k_rbc.hip, k_rs.hip); the host only checks arguments, lays out offsets and
+// moves bytes.  No CPU fallback: every hash and every code symbol is computed on the device.
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include <vector>
+
+#include "launch.h"
+#include "lcb_internal.hpp"
+#include "../../include/lachain_bls.h"
+
+using namespace lcb_int;
+
+namespace {
+
+const size_t MAX_BATCH = 65535;          // instances per call: the grid's y dimension
+const size_t MAX_ITEMS = 0x7fffffffu;
+
+bool shards_ok(int n, const char *what) {
+    if (n < 1 || n > 256) { set_error(what); return false; }
+    return true;
+}
+int depth_of(int n) {
+    int d = 0;
+    while ((1 << d) < n) d++;
+    return d;
+}
+bool monotone(const uint64_t *off, size_t n, const char *what) {
+    for (size_t i = 0; i < n; i++)
+        if (off[i + 1] < off[i]) { set_error(what); return false; }
+    return true;
+}
+void rs_matrix_lds() {
+    static bool attr = false;
+    if (attr) return;
+    (void)hipFuncSetAttribute(lcbk_rs_matrix_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, 65536 * 2);
+    (void)hipFuncSetAttribute(lcbk_rs_matrix_batch_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, 65536 * 2);
+    attr = true;
+}
+template <class T> T *upload(DevBuf &b, const T *src, size_t count, hipStream_t s) {
+    T *d = (T *)b.get(count * sizeof(T));
+    if (d && count) hipMemcpyAsync(d, src, count * sizeof(T), hipMemcpyHostToDevice, s);
+    return d;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ sizes (host arithmetic, no device)
+extern "C" size_t lcb_rbc_shard_size(size_t payload_len, int n, int f) {
+    if (n < 1 || n > 256 || f < 0 || n - 2 * f <= 0 || payload_len > 0x7fffffffu - 4) {
+        set_error("rbc shard size: need 1 <= n <= 256, 0 <= 2f < n and a payload below 2^31 - 4 bytes");
+        return 0;
+    }
+    size_t k = (size_t)(n - 2 * f);
+    return (payload_len + 4 + k - 1) / k;
+}
+extern "C" int lcb_rbc_tree_depth(int n) {
+    if (!shards_ok(n, "rbc tree depth: need 1 <= n <= 256")) return -1;
+    return depth_of(n);
+}
+
+// ------------------------------------------------------------------ ConstructValMessages
+extern "C" int lcb_rbc_val_batch(uint8_t *shards_out, uint8_t *roots_out, uint8_t *proofs_out, const uint8_t *payloads,
+                                 const uint64_t *payload_off, size_t B, int n, int f) {
+    lcb_ctx *c = ctx_sync();
+    if (!c) return -1;
+    if (n < 1 || n > 256 || f < 0 || n - 2 * f <= 0) { set_error("rbc val: need 1 <= n <= 256 and 0 <= 2f < n"); return -1; }
+    if (!B) return 0;
+    if (B > MAX_BATCH) { set_error("rbc val: at most 65535 instances per call"); return -1; }
+    if (!monotone(payload_off, B, "rbc val: offsets must not decrease")) return -1;
+    const int k = n - 2 * f, m = 2 * f, depth = depth_of(n);
+    std::vector<uint64_t> poff(B + 1), soff(B + 1);
+    size_t max_S = 0;
+    soff[0] = 0;
+    for (size_t b = 0; b < B; b++) {
+        uint64_t len = payload_off[b + 1] - payload_off[b];
+        if (len > 0x7fffffffu - 4) { set_error("rbc val: payload too long for the int32 length prefix"); return -1; }
+        size_t S = (size_t)((len + 4 + k - 1) / k);
+        max_S = S > max_S ? S : max_S;
+        soff[b + 1] = soff[b] + (uint64_t)n * S;
+    }
+    for (size_t b = 0; b <= B; b++) poff[b] = payload_off[b] - payload_off[0];
+    Enq q(c, c->stream);
+    hipStream_t s = c->stream;
+    const uint8_t *dpay = upload(c->rbc[0], payloads + payload_off[0], (size_t)poff[B], s);
+    const uint64_t *dpoff = upload(c->rbc[1], poff.data(), B + 1, s);
+    const uint64_t *dsoff = upload(c->rbc[2], soff.data(), B + 1, s);
+    uint8_t *dsh = (uint8_t *)c->rbc[3].get((size_t)soff[B]);
+    int *dpos = (int *)c->rbc[4].get(4 * (size_t)n);
+    uint8_t *dM = (uint8_t *)c->rbc[5].get((size_t)m * k + 16);
+    uint8_t *droots = (uint8_t *)c->rbc[7].get(32 * B);
+    uint8_t *dproofs = (uint8_t *)c->rbc[8].get(32 * B * n * (size_t)depth);
+    if (!dpay || !dpoff || !dsoff || !dsh || !dpos || !dM || !droots || !dproofs) {
+        set_error("device allocation failed");
+        return -1;
+    }
+    lcbk_rbc_augment(s, dpay, dpoff, dsh, dsoff, n, k, max_S * k, (unsigned)B);
+    uint8_t *dok = dM + (size_t)m * k;
+    uint8_t ok = 1;
+    if (m) {
+        rs_matrix_lds();
+        std::vector<int> pos(n);
+        for (int j = 0; j < m; j++) pos[j] = k + j;          // unknown: the parity positions
+        for (int j = 0; j < k; j++) pos[m + j] = j;
+        hipMemcpyAsync(dpos, pos.data(), 4 * (size_t)n, hipMemcpyHostToDevice, s);
+        lcbk_rs_matrix(s, dpos, m, dpos + m, k, n, dM, dok);
+        lcbk_rs_apply_batch(s, dM, 0, dok, 0, m, k, n, dsh, dsoff, dpos, 0, dsh, dsoff, 0, max_S, (unsigned)B);
+        hipMemcpyAsync(&ok, dok, 1, hipMemcpyDeviceToHost, s);
+    }
+    lcbk_rbc_tree(s, dsh, dsoff, n, depth, nullptr, droots, depth ? dproofs : nullptr, (unsigned)B);
+    if (!launch_ok("rbc val launch")) return -1;
+    if (shards_out) hipMemcpyAsync(shards_out, dsh, (size_t)soff[B], hipMemcpyDeviceToHost, s);
+    if (roots_out) hipMemcpyAsync(roots_out, droots, 32 * B, hipMemcpyDeviceToHost, s);
+    if (proofs_out && depth) hipMemcpyAsync(proofs_out, dproofs, 32 * B * n * (size_t)depth, hipMemcpyDeviceToHost, s);
+    if (!sync_ok(c, "rbc val")) return -1;
+    if (!ok) { set_error("rbc val: parity positions are not independent"); return -1; }
+    return 0;
+}
+
+// ------------------------------------------------------------------ CheckEchoMessage
+extern "C" int lcb_ctx_rbc_check_echo_dev(lcb_ctx *ctx, uint8_t *accept, const uint8_t *data, const uint64_t *data_off,
+                                          const int32_t *from, const uint8_t *roots, const uint8_t *proofs,
+                                          const uint64_t *proof_off, size_t n_items, int n_shards, void *stream) {
+    lcb_ctx *c = ctx_resolve(ctx);
+    if (!c) return -1;
+    if (!shards_ok(n_shards, "rbc check echo: need 1 <= n_shards <= 256")) return -1;
+    if (n_items > MAX_ITEMS) { set_error("rbc check echo: batch too large"); return -1; }
+    Enq q(c, (hipStream_t)stream);
+    if (!n_items) return 0;
+    lcbk_rbc_echo(q.s, accept, data, data_off, from, roots, proofs, proof_off, (u32)n_items, n_shards);
+    return launch_ok("rbc check echo launch") ? 0 : -1;
+}
+extern "C" int lcb_rbc_check_echo_dev(uint8_t *accept, const uint8_t *data, const uint64_t *data_off, const int32_t *from,
+                                      const uint8_t *roots, const uint8_t *proofs, const uint64_t *proof_off,
+                                      size_t n_items, int n_shards, void *stream) {
+    return lcb_ctx_rbc_check_echo_dev(nullptr, accept, data, data_off, from, roots, proofs, proof_off, n_items, n_shards,
+                                      stream);
+}
+extern "C" int lcb_rbc_check_echo_batch(uint8_t *accept, const uint8_t *data, const uint64_t *data_off, const int32_t *from,
+                                        const uint8_t *roots, const uint8_t *proofs, const uint64_t *proof_off,
+                                        size_t n_items, int n_shards) {
+    lcb_ctx *c = ctx_sync();
+    if (!c) return -1;
+    if (!shards_ok(n_shards, "rbc check echo: need 1 <= n_shards <= 256")) return -1;
+    if (!n_items) return 0;
+    if (n_items > MAX_ITEMS) { set_error("rbc check echo: batch too large"); return -1; }
+    if (!monotone(data_off, n_items, "rbc check echo: data offsets must not decrease") ||
+        !monotone(proof_off, n_items, "rbc check echo: proof offsets must not decrease"))
+        return -1;
+    std::vector<uint64_t> doff(n_items + 1), poff(n_items + 1);
+    for (size_t i = 0; i <= n_items; i++) { doff[i] = data_off[i] - data_off[0]; poff[i] = proof_off[i] - proof_off[0]; }
+    Enq q(c, c->stream);
+    hipStream_t s = c->stream;
+    const uint8_t *dd = upload(c->rbc[0], data + data_off[0], (size_t)doff[n_items], s);
+    const uint64_t *ddoff = upload(c->rbc[1], doff.data(), n_items + 1, s);
+    const uint64_t *dpoff = upload(c->rbc[2], poff.data(), n_items + 1, s);
+    const int32_t *dfrom = upload(c->rbc[4], from, n_items, s);
+    const uint8_t *dpr = upload(c->rbc[10], proofs + 32 * proof_off[0], 32 * (size_t)poff[n_items], s);
+    const uint8_t *droots = upload(c->rbc[11], roots, 32 * n_items, s);
+    uint8_t *dacc = (uint8_t *)c->rbc[9].get(n_items);
+    if (!dd || !ddoff || !dpoff || !dfrom || !dpr || !droots || !dacc) { set_error("device allocation failed"); return -1; }
+    if (lcb_ctx_rbc_check_echo_dev(c, dacc, dd, ddoff, dfrom, droots, dpr, dpoff, n_items, n_shards, s)) return -1;
+    hipMemcpyAsync(accept, dacc, n_items, hipMemcpyDeviceToHost, s);
+    return sync_ok(c, "rbc check echo") ? 0 : -1;
+}
+
+// ------------------------------------------------------------------ ConstructMerkleTree
+extern "C" int lcb_ctx_rbc_merkle_tree_dev(lcb_ctx *ctx, uint8_t *trees_out, const uint8_t *shards,
+                                           const uint64_t *shard_off, size_t B, int n_shards, void *stream) {
+    lcb_ctx *c = ctx_resolve(ctx);
+    if (!c) return -1;
+    if (!shards_ok(n_shards, "rbc merkle tree: need 1 <= n_shards <= 256")) return -1;
+    if (B > MAX_ITEMS) { set_error("rbc merkle tree: batch too large"); return -1; }
+    if (((uintptr_t)trees_out) & 7) { set_error("rbc merkle tree: trees_out must be 8-byte aligned"); return -1; }
+    Enq q(c, (hipStream_t)stream);
+    if (!B) return 0;
+    lcbk_rbc_tree(q.s, shards, shard_off, n_shards, depth_of(n_shards), trees_out, nullptr, nullptr, (unsigned)B);
+    return launch_ok("rbc merkle tree launch") ? 0 : -1;
+}
+extern "C" int lcb_rbc_merkle_tree_dev(uint8_t *trees_out, const uint8_t *shards, const uint64_t *shard_off, size_t B,
+                                       int n_shards, void *stream) {
+    return lcb_ctx_rbc_merkle_tree_dev(nullptr, trees_out, shards, shard_off, B, n_shards, stream);
+}
+extern "C" int lcb_rbc_merkle_tree_batch(uint8_t *trees_out, const uint8_t *shards, const uint64_t *shard_off, size_t B,
+                                         int n_shards) {
+    lcb_ctx *c = ctx_sync();
+    if (!c) return -1;
+    if (!shards_ok(n_shards, "rbc merkle tree: need 1 <= n_shards <= 256")) return -1;
+    if (!B) return 0;
+    if (B > MAX_ITEMS) { set_error("rbc merkle tree: batch too large"); return -1; }
+    if (!monotone(shard_off, B, "rbc merkle tree: offsets must not decrease")) return -1;
+    std::vector<uint64_t> off(B + 1);
+    for (size_t b = 0; b <= B; b++) off[b] = shard_off[b] - shard_off[0];
+    for (size_t b = 0; b < B; b++)
+        if ((off[b + 1] - off[b]) % (uint64_t)n_shards) {
+            set_error("rbc merkle tree: an instance's bytes are not n_shards equal shards");
+            return -1;
+        }
+    const size_t tree_bytes = 64 * ((size_t)1 << depth_of(n_shards));
+    Enq q(c, c->stream);
+    hipStream_t s = c->stream;
+    const uint8_t *dsh = upload(c->rbc[0], shards + shard_off[0], (size_t)off[B], s);
+    const uint64_t *doff = upload(c->rbc[1], off.data(), B + 1, s);
+    uint8_t *dtrees = (uint8_t *)c->rbc[8].get(tree_bytes * B);
+    if (!dsh || !doff || !dtrees) { set_error("device allocation failed"); return -1; }
+    if (lcb_ctx_rbc_merkle_tree_dev(c, dtrees, dsh, doff, B, n_shards, s)) return -1;
+    hipMemcpyAsync(trees_out, dtrees, tree_bytes * B, hipMemcpyDeviceToHost, s);
+    return sync_ok(c, "rbc merkle tree") ? 0 : -1;
+}
+
+// ------------------------------------------------------------------ TrySendReadyMessageFromEchos
+extern "C" int lcb_rbc_decode_batch(uint8_t *shards_out, uint8_t *status, uint8_t *root_ok, uint8_t *roots_out,
+                                    const uint8_t *echo_data, const uint64_t *echo_off, const int32_t *from,
+                                    const uint8_t *expected_roots, size_t B, int n, int f) {
+    lcb_ctx *c = ctx_sync();
+    if (!c) return -1;
+    if (n < 1 || n > 256 || f < 0 || n - 2 * f <= 0) { set_error("rbc decode: need 1 <= n <= 256 and 0 <= 2f < n"); return -1; }
+    if (!B) return 0;
+    if (B > MAX_BATCH) { set_error("rbc decode: at most 65535 instances per call"); return -1; }
+    if (!status) { set_error("rbc decode: status is required"); return -1; }
+    if (!monotone(echo_off, B, "rbc decode: offsets must not decrease")) return -1;
+    const int k = n - 2 * f, m = 2 * f, depth = depth_of(n);
+    std::vector<uint64_t> eoff(B + 1), soff(B + 1);
+    size_t max_S = 0;
+    soff[0] = 0;
+    for (size_t b = 0; b <= B; b++) eoff[b] = echo_off[b] - echo_off[0];
+    for (size_t b = 0; b < B; b++) {
+        uint64_t bytes = eoff[b + 1] - eoff[b];
+        if (bytes % (uint64_t)k) { set_error("rbc decode: an instance's bytes are not n - 2f equal echoes"); return -1; }
+        size_t S = (size_t)(bytes / k);
+        max_S = S > max_S ? S : max_S;
+        soff[b + 1] = soff[b] + (uint64_t)n * S;
+    }
+    // per instance: the erased positions, then the echoes' positions in echo order; an instance with a bad or duplicate
+    // index gets the identity (its output is zeroed through valid[b] = 0)
+    std::vector<int> pos(B * (size_t)n);
+    std::vector<uint8_t> valid(B, 1), have(n);
+    for (size_t b = 0; b < B; b++) {
+        int *p = &pos[b * (size_t)n];
+        memset(have.data(), 0, n);
+        for (int e = 0; e < k && valid[b]; e++) {
+            int32_t j = from[b * (size_t)k + e];
+            if (j < 0 || j >= n || have[j]) valid[b] = 0;
+            else { have[j] = 1; p[m + e] = j; }
+        }
+        if (valid[b]) {
+            int w = 0;
+            for (int j = 0; j < n; j++) if (!have[j]) p[w++] = j;
+        } else {
+            for (int j = 0; j < n; j++) p[j] = j;
+        }
+    }
+    Enq q(c, c->stream);
+    hipStream_t s = c->stream;
+    rs_matrix_lds();
+    const uint8_t *decho = upload(c->rbc[0], echo_data + echo_off[0], (size_t)eoff[B], s);
+    const uint64_t *deoff = upload(c->rbc[1], eoff.data(), B + 1, s);
+    const uint64_t *dsoff = upload(c->rbc[2], soff.data(), B + 1, s);
+    uint8_t *dsh = (uint8_t *)c->rbc[3].get((size_t)soff[B]);
+    const int *dpos = upload(c->rbc[4], pos.data(), pos.size(), s);
+    uint8_t *dM = (uint8_t *)c->rbc[5].get(B * (size_t)m * k + B);
+    const uint8_t *dvalid = upload(c->rbc[6], valid.data(), B, s);
+    uint8_t *droots = (uint8_t *)c->rbc[7].get(32 * B);
+    if (!decho || !deoff || !dsoff || !dsh || !dpos || !dM || !dvalid || !droots) {
+        set_error("device allocation failed");
+        return -1;
+    }
+    uint8_t *dok = dM + B * (size_t)m * k;
+    lcbk_rs_matrix_batch(s, dpos, m, k, n, dvalid, dM, dok, (unsigned)B);
+    lcbk_rs_apply_batch(s, dM, (size_t)m * k, dok, 1, m, k, n, decho, deoff, dpos, (size_t)n, dsh, dsoff, k, max_S,
+                        (unsigned)B);
+    lcbk_rbc_tree(s, dsh, dsoff, n, depth, nullptr, droots, nullptr, (unsigned)B);
+    if (!launch_ok("rbc decode launch")) return -1;
+    std::vector<uint8_t> roots(32 * B);
+    if (shards_out) hipMemcpyAsync(shards_out, dsh, (size_t)soff[B], hipMemcpyDeviceToHost, s);
+    hipMemcpyAsync(status, dok, B, hipMemcpyDeviceToHost, s);
+    hipMemcpyAsync(roots.data(), droots, 32 * B, hipMemcpyDeviceToHost, s);
+    if (!sync_ok(c, "rbc decode")) return -1;
+    for (size_t b = 0; b < B; b++) {
+        status[b] = status[b] ? 1 : 0;
+        if (!status[b]) memset(&roots[32 * b], 0, 32);
+        if (root_ok) root_ok[b] = status[b] && expected_roots && !memcmp(&roots[32 * b], expected_roots + 32 * b, 32);
+    }
+    if (roots_out) memcpy(roots_out, roots.data(), 32 * B);
+    return 0;
+}
+
+// ------------------------------------------------------------------ MerkleTree.ComputeRoot
+extern "C" int lcb_ctx_merkle_root_dev(lcb_ctx *ctx, uint8_t *roots_out, uint8_t *status, const uint8_t *hashes,
+                                       const uint64_t *off, size_t n_trees, size_t n_hashes, void *stream) {
+    lcb_ctx *c = ctx_resolve(ctx);
+    if (!c) return -1;
+    if (n_trees > MAX_ITEMS) { set_error("merkle root: batch too large"); return -1; }
+    Enq q(c, (hipStream_t)stream);
+    if (!n_trees) return 0;
+    uint8_t *ws = (uint8_t *)c->rbc[8].get(32 * n_hashes);
+    if (!ws) { set_error("device allocation failed"); return -1; }
+    lcbk_merkle_root(q.s, roots_out, status, hashes, off, ws, (unsigned)n_trees);
+    return launch_ok("merkle root launch") ? 0 : -1;
+}
+extern "C" int lcb_merkle_root_dev(uint8_t *roots_out, uint8_t *status, const uint8_t *hashes, const uint64_t *off,
+                                   size_t n_trees, size_t n_hashes, void *stream) {
+    return lcb_ctx_merkle_root_dev(nullptr, roots_out, status, hashes, off, n_trees, n_hashes, stream);
+}
+extern "C" int lcb_merkle_root_batch(uint8_t *roots_out, uint8_t *status, const uint8_t *hashes, const uint64_t *off,
+                                     size_t n_trees) {
+    lcb_ctx *c = ctx_sync();
+    if (!c) return -1;
+    if (!n_trees) return 0;
+    if (n_trees > MAX_ITEMS) { set_error("merkle root: batch too large"); return -1; }
+    if (!monotone(off, n_trees, "merkle root: offsets must not decrease")) return -1;
+    std::vector<uint64_t> rel(n_trees + 1);
+    for (size_t t = 0; t <= n_trees; t++) rel[t] = off[t] - off[0];
+    Enq q(c, c->stream);
+    hipStream_t s = c->stream;
+    const uint8_t *dh = upload(c->rbc[0], hashes + 32 * off[0], 32 * (size_t)rel[n_trees], s);
+    const uint64_t *doff = upload(c->rbc[1], rel.data(), n_trees + 1, s);
+    uint8_t *droots = (uint8_t *)c->rbc[7].get(32 * n_trees), *dst = (uint8_t *)c->rbc[9].get(n_trees);
+    if (!dh || !doff || !droots || !dst) { set_error("device allocation failed"); return -1; }
+    if (lcb_ctx_merkle_root_dev(c, droots, dst, dh, doff, n_trees, (size_t)rel[n_trees], s)) return -1;
+    hipMemcpyAsync(roots_out, droots, 32 * n_trees, hipMemcpyDeviceToHost, s);
+    hipMemcpyAsync(status, dst, n_trees, hipMemcpyDeviceToHost, s);
+    return sync_ok(c, "merkle root") ? 0 : -1;
+}

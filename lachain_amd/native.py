@@ -18,6 +18,7 @@ _lock = threading.Lock()
 
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_u32p = ctypes.POINTER(ctypes.c_uint32)
+c_u64p = ctypes.POINTER(ctypes.c_uint64)
 c_size = ctypes.c_size_t
 
 
@@ -210,6 +211,18 @@ _SIGS = {
     "lcb_ecdsa_recover_phase_ms": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float)]),
     "lcb_keccak256_batch": (ctypes.c_int, [c_u8p, c_u8p, ctypes.POINTER(ctypes.c_uint64), c_size]),
     "lcb_keccak256_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_size, ctypes.c_void_p]),
+    "lcb_rbc_shard_size": (c_size, [c_size, ctypes.c_int, ctypes.c_int]),
+    "lcb_rbc_tree_depth": (ctypes.c_int, [ctypes.c_int]),
+    "lcb_rbc_val_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u64p, c_size, ctypes.c_int, ctypes.c_int]),
+    "lcb_rbc_check_echo_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u64p, ctypes.POINTER(ctypes.c_int32), c_u8p, c_u8p,
+                                                c_u64p, c_size, ctypes.c_int]),
+    "lcb_rbc_check_echo_dev": (ctypes.c_int, [ctypes.c_void_p] * 7 + [c_size, ctypes.c_int, ctypes.c_void_p]),
+    "lcb_rbc_merkle_tree_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u64p, c_size, ctypes.c_int]),
+    "lcb_rbc_merkle_tree_dev": (ctypes.c_int, [ctypes.c_void_p] * 3 + [c_size, ctypes.c_int, ctypes.c_void_p]),
+    "lcb_rbc_decode_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u64p, ctypes.POINTER(ctypes.c_int32),
+                                            c_u8p, c_size, ctypes.c_int, ctypes.c_int]),
+    "lcb_merkle_root_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u64p, c_size]),
+    "lcb_merkle_root_dev": (ctypes.c_int, [ctypes.c_void_p] * 4 + [c_size, c_size, ctypes.c_void_p]),
     "lcb_ctx_create": (ctypes.c_void_p, []),
     "lcb_ctx_destroy": (None, [ctypes.c_void_p]),
     "lcb_ctx_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
@@ -221,7 +234,8 @@ for _name in ("tpke_prepare_dev", "tpke_verify_prepared_dev", "tpke_verify_prepa
               "g2_lagrange_dev", "g1_msm_dev", "g1_msm_glv_dev", "g1_msm_phase_ms", "g1_jac_sum_dev", "ecdsa_verify_hashed_dev",
               "root_header_verify_dev", "ecdsa_pubkey_dev", "ecdsa_sign_hashed_dev", "ecdsa_phase_ms", "batched_census",
               "tpke_combine_ordered_dev", "ts_assemble_ordered_dev", "ecdsa_recover_hashed_dev",
-              "ecdsa_special_recover_hashed_dev", "tx_verify_dev", "ecdsa_recover_phase_ms", "keccak256_dev"):
+              "ecdsa_special_recover_hashed_dev", "tx_verify_dev", "ecdsa_recover_phase_ms", "keccak256_dev",
+              "rbc_check_echo_dev", "rbc_merkle_tree_dev", "merkle_root_dev"):
     _res, _args = _SIGS["lcb_" + _name]
     _SIGS["lcb_ctx_" + _name] = (_res, [ctypes.c_void_p] + list(_args))
 
@@ -676,6 +690,105 @@ def keccak256_batch(msgs) -> bytes:
     ob, po = _out(32 * n)
     _check(lib().lcb_keccak256_batch(po, pd, offs, n), "keccak256_batch")
     return bytes(ob)[: 32 * n]
+
+
+# ---------------------------------------------------------------- reliable broadcast: Merkle layer (§8f row 3)
+def _u64_keep(keep, vals):
+    arr = (ctypes.c_uint64 * max(1, len(vals)))(*vals)
+    keep.append(arr)
+    return ctypes.cast(arr, c_u64p)
+
+
+def rbc_shard_size(payload_len: int, n: int, f: int) -> int:
+    """AugmentInput's shard size; host arithmetic, needs no device"""
+    s = load(False).lcb_rbc_shard_size(payload_len, n, f)
+    if s == 0:
+        raise RuntimeError("liblachain_bls rbc_shard_size failed: " + load(False).lcb_last_error().decode())
+    return s
+
+
+def rbc_tree_depth(n: int) -> int:
+    d = load(False).lcb_rbc_tree_depth(n)
+    if d < 0:
+        raise RuntimeError("liblachain_bls rbc_tree_depth failed: " + load(False).lcb_last_error().decode())
+    return d
+
+
+def rbc_val_batch(payloads, n: int, f: int):
+    """ConstructValMessages for each payload: (shards, roots, proofs) as flat bytes — n * S_b bytes per instance in
+    order, 32 bytes per instance, n * depth * 32 bytes per instance"""
+    B = len(payloads)
+    if not (1 <= n <= 256 and f >= 0 and n - 2 * f > 0):       # the library words the error
+        _check(lib().lcb_rbc_val_batch(None, None, None, None, None, 0, n, f), "rbc_val_batch")
+    k, depth = n - 2 * f, rbc_tree_depth(n)
+    total = sum((len(p) + 4 + k - 1) // k * n for p in payloads)
+    keep = []
+    _, pp = _bytes_ptr_keep(keep, b"".join(payloads))
+    po = _u64_keep(keep, _offsets(payloads))
+    sb, ps = _out(total)
+    rb, pr = _out(32 * B)
+    fb, pf = _out(32 * B * n * depth)
+    _check(lib().lcb_rbc_val_batch(ps, pr, pf, pp, po, B, n, f), "rbc_val_batch")
+    return bytes(sb)[:total], bytes(rb)[: 32 * B], bytes(fb)[: 32 * B * n * depth]
+
+
+def rbc_check_echo_batch(data, data_off, frm, roots: bytes, proofs: bytes, proof_off, n_shards: int) -> bytes:
+    """CheckEchoMessage per item: data_off in bytes, proof_off in hashes (one entry more than items); one byte each"""
+    n = len(frm)
+    keep = []
+    _, pd = _bytes_ptr_keep(keep, data)
+    _, pr = _bytes_ptr_keep(keep, roots)
+    _, pp = _bytes_ptr_keep(keep, proofs)
+    ob, po = _out(n)
+    _check(lib().lcb_rbc_check_echo_batch(po, pd, _u64_keep(keep, data_off), _i32_keep(keep, frm), pr, pp,
+                                          _u64_keep(keep, proof_off), n, n_shards), "rbc_check_echo_batch")
+    return bytes(ob)[:n]
+
+
+def rbc_merkle_tree_batch(shards: bytes, shard_off, n_shards: int) -> bytes:
+    """ConstructMerkleTree per instance (n_shards equal shards each): 2T x 32 bytes per instance, node 0 zero"""
+    B = len(shard_off) - 1
+    keep = []
+    _, ps = _bytes_ptr_keep(keep, shards)
+    size = 64 * (1 << rbc_tree_depth(n_shards)) * B
+    ob, po = _out(size)
+    _check(lib().lcb_rbc_merkle_tree_batch(po, ps, _u64_keep(keep, shard_off), B, n_shards), "rbc_merkle_tree_batch")
+    return bytes(ob)[:size]
+
+
+def rbc_decode_batch(echo_data: bytes, echo_off, frm, expected_roots, n: int, f: int):
+    """TrySendReadyMessageFromEchos' work per instance: (shards, status, root_ok, roots) as flat bytes; frm holds
+    n - 2f indices per instance; expected_roots (32 bytes per instance) may be None"""
+    B = len(echo_off) - 1
+    k = n - 2 * f
+    keep = []
+    _, pd = _bytes_ptr_keep(keep, echo_data)
+    pe = None
+    if expected_roots is not None:
+        _, pe = _bytes_ptr_keep(keep, expected_roots)
+    total = (echo_off[-1] - echo_off[0]) // k * n if k > 0 else 0
+    sb, ps = _out(total)
+    stb, pst = _out(B)
+    okb, pok = _out(B)
+    rb, pr = _out(32 * B)
+    _check(lib().lcb_rbc_decode_batch(ps, pst, pok, pr, pd, _u64_keep(keep, echo_off), _i32_keep(keep, frm), pe, B, n, f),
+           "rbc_decode_batch")
+    return bytes(sb)[:total], bytes(stb)[:B], bytes(okb)[:B], bytes(rb)[: 32 * B]
+
+
+def merkle_root_batch(trees):
+    """MerkleTree.ComputeRoot per list of 32-byte hashes: the root, or None for an empty list"""
+    n = len(trees)
+    keep = []
+    _, ph = _bytes_ptr_keep(keep, b"".join(b"".join(t) for t in trees))
+    off = [0]
+    for t in trees:
+        off.append(off[-1] + len(t))
+    rb, pr = _out(32 * n)
+    sb, ps = _out(n)
+    _check(lib().lcb_merkle_root_batch(pr, ps, ph, _u64_keep(keep, off), n), "merkle_root_batch")
+    r = bytes(rb)
+    return [r[32 * t:32 * t + 32] if sb[t] else None for t in range(n)]
 
 
 class EcdsaKeySet:
