@@ -339,6 +339,14 @@ int lcb_set_coop_max(uint32_t max_checks);
 /* the cooperative threshold of the group Miller loops alone (default 65536; the final exponentiations keep
    lcb_set_coop_max's) */
 int lcb_set_coop_miller_max(uint32_t max_checks);
+/* level 1 of the TPKE batched check: chunks of at least min_entries entries run one final exponentiation per pair of
+   randomized groups (a second pass exponentiates one member of each pair that failed; the other's value is the
+   quotient), instead of one per group.  0 = never; UINT32_MAX (the default) = more entries than lcb_set_coop_max's
+   value.  Decisions are unchanged.  Tuning hook (LCB_ALLOW_TUNING=1). */
+int lcb_set_fe_pair_min(uint32_t min_entries);
+/* that stage in the calling thread's last batched verify (lcb_ctx_ form: that context's last one): {pairs formed,
+   pairs that failed, final exponentiations run in pass 1, in pass 2}; all 0 when the stage did not run */
+int lcb_tpke_fe_pair_stats(uint32_t out[4]);
 /* shares / group checks per Miller + final-exponentiation launch pair (default and maximum 2^21): a test hook that
    makes small batches run several chunks (chunk offsets in the copies and searches).  Set it only while no batch call
    is in flight.  Tuning hook (LCB_ALLOW_TUNING=1). */
@@ -424,6 +432,7 @@ int lcb_ctx_tpke_verify_shares_batched_dev(lcb_ctx *ctx, uint8_t *accept, size_t
                                            void *stream);
 int lcb_ctx_tpke_batched_stats(lcb_ctx *ctx, uint32_t levels[8], float ms[6]);
 int lcb_ctx_batched_census(lcb_ctx *ctx, uint32_t out[4]);
+int lcb_ctx_tpke_fe_pair_stats(lcb_ctx *ctx, uint32_t out[4]);
 int lcb_ctx_ts_verify_prepared_batched_dev(lcb_ctx *ctx, uint8_t *accept, size_t n, size_t n_pks, size_t n_msgs,
                                            const uint8_t *sigs, const uint32_t *msg_idx, const uint32_t *pk_idx,
                                            void *stream);

@@ -351,3 +351,129 @@ extern "C" void lcbk_tpke_rlc_search2b_asm(hipStream_t s, const void *search, u3
     LCB_LAUNCH_GATED(k_tpke_rlc_search2b_asm, dim3((n_open + 1) / 2), dim3(64), 0, s, (const uint4 *)search, ns, gamma0,
                      gamma12, open, open_count, accept, (uint4 *)next, next_count, key_idx, n_keys, susp, park);
 }
+
+// ================================================================================= level-1 pair stage (TPKE)
+// One final exponentiation per pair of level-1 groups (lcb_host.cpp rlc_checks).  The final exponentiation is a
+// homomorphism and every share's exponent is secret and independent, so FE(f_a f_b) = 1 accepts groups a and b
+// together (k_batch.hip header: a bad group passes only if gamma_a gamma_b = 1, one value of one exponent).  Job j of a
+// chunk of m entries covers entries a = 2j and b = 2j + 1, and holds one slot of the pair park (stride J = jobs):
+//   kind 0  both randomized groups (desc.w == 0): the slot takes f_a f_b.  If its final exponentiation is not 1, pass 2
+//           exponentiates f_a alone and gamma_b = gamma_ab conj(gamma_a) (the values are unitary after the easy part).
+//   kind 1  an exact single (desc.w == 1) among the two: no product.  The slot takes f_b, pass 2 always takes f_a, so
+//           each keeps an exponentiation of its own.
+//   kind 2  the odd last entry: the slot takes f_a.
+// Every product runs on lcb_asm_fp12_mul_n over park slots, on canonical values, so gamma_b has the words a direct
+// exponentiation of f_b gives.  The call is per wave: the lanes past the last job have left (as in k_final_exp_check),
+// the lanes of a wave without a product of their own multiply by one, and a wave with no product at all (a level of
+// exact singles) copies its values instead.
+extern "C" __global__ void __launch_bounds__(64) k_fe_pair_pack(const uint4 *desc, const u32 *f, u32 m, u32 *park,
+                                                               u32 jobs, uint8_t *kind, uint8_t *pacc) {
+    __shared__ uint4 lds[36 * 64];
+    LCB_LATENCY_PRIO();
+    const u32 j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= jobs) return;
+    const u32 a = 2 * j, b = 2 * j + 1;
+    const u32 k = b >= m ? 2u : (desc[a].w == 0 && desc[b].w == 0) ? 0u : 1u;
+    u32 *S0 = park, *S1 = park + (size_t)144 * jobs, *S2 = park + (size_t)288 * jobs;
+    fp12 t;
+    if (__ballot(k == 0) != 0) {         // (wave-uniform)
+        if (k == 1) t = fp12_one();
+        else fp12_load_soa(t, f, m, a);
+        fp12_store_soa(S1, jobs, j, t);
+        if (k == 2) t = fp12_one();
+        else fp12_load_soa(t, f, m, b);
+        fp12_store_soa(S2, jobs, j, t);
+        lcb_asm_fp12_mul_n(S1, 0, S2, S0, S0, jobs * 16, j * 16, lane_lds36(lds));
+    } else {
+        fp12_load_soa(t, f, m, k == 1 ? b : a);
+        fp12_store_soa(S0, jobs, j, t);
+    }
+    kind[j] = (uint8_t)k;
+    pacc[j] = k == 1 ? 0 : 1;
+}
+// after pass 1: the jobs whose first entry needs an exponentiation of its own -> list (p2idx[j] = the job's place in
+// it); cnt: [0] the list's length, [1] pairs formed, [2] pairs that failed
+extern "C" __global__ void LCB_BOUNDS k_fe_pair_list(const uint8_t *kind, const uint8_t *pacc, u32 jobs, u32 *list,
+                                                    u32 *p2idx, u32 *cnt) {
+    LCB_LATENCY_PRIO();
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= jobs) return;
+    const u32 k = kind[j];
+    if (k == 0) atomicAdd(cnt + 1, 1u);
+    if (k == 2 || pacc[j]) return;
+    if (k == 0) atomicAdd(cnt + 2, 1u);
+    const u32 p = atomicAdd(cnt, 1u);
+    list[p] = j;
+    p2idx[j] = p;
+}
+// pass 2's inputs: f of the first entry of the n2 listed jobs -> slot 0 of park2 (stride n2)
+extern "C" __global__ void LCB_BOUNDS k_fe_pair_gather(const u32 *f, u32 m, const u32 *list, u32 n2, u32 *park2,
+                                                      uint8_t *pacc2) {
+    LCB_LATENCY_PRIO();
+    const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n2) return;
+    fp12 t;
+    fp12_load_soa(t, f, m, 2 * list[p]);
+    fp12_store_soa(park2, n2, p, t);
+    pacc2[p] = 1;
+}
+// after pass 2: the final-exponentiation values of the entries that were not accepted in a pair -> their rows of the
+// chunk's park f (slot 0, stride m: what k_rlc_resolve reads), and gacc[i] = gacc[i] && gamma_i == 1 for them; the
+// members of a pair that passed keep gacc (and k_rlc_resolve never reads their rows)
+extern "C" __global__ void __launch_bounds__(64) k_fe_pair_finish(u32 *f, u32 m, u32 *park, u32 jobs,
+                                                                 const uint8_t *kind, const uint8_t *pacc,
+                                                                 const u32 *p2idx, const u32 *park2, u32 n2,
+                                                                 uint8_t *gacc) {
+    __shared__ uint4 lds[36 * 64];
+    LCB_LATENCY_PRIO();
+    const u32 j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= jobs) return;
+    const u32 k = kind[j], a = 2 * j, b = 2 * j + 1;
+    const bool second = k != 2 && !pacc[j];        // the job had an exponentiation in pass 2
+    const u32 p = second ? p2idx[j] : 0;
+    u32 *S1 = park + (size_t)144 * jobs, *S3 = park + (size_t)432 * jobs;
+    fp12 t;
+    // G: where the job's slot value stands, divided by gamma_a for a failed pair.  A wave with a failed pair forms the
+    // quotients in slot 3 (its other lanes divide by one); a wave without one reads slot 0 as it is.
+    const u32 *G = park;
+    if (__ballot(k == 0 && second) != 0) {          // (wave-uniform)
+        if (k == 0 && second) fp12_load_soa(t, park2, n2, p);
+        else t = fp12_one();
+        fp12_store_soa(S1, jobs, j, t);
+        lcb_asm_fp12_mul_n(S1, 1, park, S3, S3, jobs * 16, j * 16, lane_lds36(lds));   // slot 0 conj(gamma_a)
+        G = S3;
+    }
+    if (k == 2) {
+        fp12_load_soa_fresh(t, G, jobs, j);
+        fp12_store_soa(f, m, a, t);
+        gacc[a] = gacc[a] && fp12_is_one(t);
+    } else if (second) {
+        fp12_load_soa_fresh(t, G, jobs, j);
+        fp12_store_soa(f, m, b, t);
+        gacc[b] = gacc[b] && fp12_is_one(t);
+        fp12_load_soa(t, park2, n2, p);
+        fp12_store_soa(f, m, a, t);
+        gacc[a] = gacc[a] && fp12_is_one(t);
+    }
+}
+extern "C" void lcbk_fe_pair_pack(hipStream_t s, const void *desc, const u32 *f, u32 m, u32 *park, u32 jobs,
+                                  uint8_t *kind, uint8_t *pacc) {
+    LCB_LAUNCH_GATED(k_fe_pair_pack, dim3((jobs + 63) / 64), dim3(64), 0, s, (const uint4 *)desc, f, m, park, jobs,
+                     kind, pacc);
+}
+extern "C" void lcbk_fe_pair_list(hipStream_t s, const uint8_t *kind, const uint8_t *pacc, u32 jobs, u32 *list,
+                                  u32 *p2idx, u32 *cnt) {
+    dim3 grid((jobs + LCB_BLOCK - 1) / LCB_BLOCK);
+    LCB_LAUNCH(k_fe_pair_list, kind, pacc, jobs, list, p2idx, cnt);
+}
+extern "C" void lcbk_fe_pair_gather(hipStream_t s, const u32 *f, u32 m, const u32 *list, u32 n2, u32 *park2,
+                                    uint8_t *pacc2) {
+    if (!n2) return;
+    dim3 grid((n2 + LCB_BLOCK - 1) / LCB_BLOCK);
+    LCB_LAUNCH(k_fe_pair_gather, f, m, list, n2, park2, pacc2);
+}
+extern "C" void lcbk_fe_pair_finish(hipStream_t s, u32 *f, u32 m, u32 *park, u32 jobs, const uint8_t *kind,
+                                    const uint8_t *pacc, const u32 *p2idx, const u32 *park2, u32 n2, uint8_t *gacc) {
+    LCB_LAUNCH_GATED(k_fe_pair_finish, dim3((jobs + 63) / 64), dim3(64), 0, s, f, m, park, jobs, kind, pacc, p2idx,
+                     park2, n2, gacc);
+}

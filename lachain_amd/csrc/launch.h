@@ -121,6 +121,12 @@ extern "C" int lcbk_search2b_debug(void *p);
 extern "C" void lcbk_tpke_rlc_search2b(hipStream_t s, const void *search, u32 ns, u32 n_open, const u32 *gamma0, const u32 *gamma12, const u32 *open, const u32 *open_count, uint8_t *accept, void *next, u32 *next_count, const u32 *key_idx, u32 n_keys, const u32 *susp);
 extern "C" void lcbk_tpke_rlc_search2b_asm(hipStream_t s, const void *search, u32 ns, u32 n_open, const u32 *gamma0, const u32 *gamma12, const u32 *open, const u32 *open_count, uint8_t *accept, void *next, u32 *next_count, const u32 *key_idx, u32 n_keys, const u32 *susp, u32 *park);
 extern "C" size_t lcbk_tpke_rlc_search2b_asm_park_bytes(u32 n_open);
+// level-1 pair stage (k_tpke.hip; host side lcb_host.cpp rlc_fe_pairs, switched by lcb_set_fe_pair_min and counted by
+// lcb_ctx_tpke_fe_pair_stats): jobs = ceil(m / 2) slots of the pair park, n2 = the jobs listed for pass 2
+extern "C" void lcbk_fe_pair_pack(hipStream_t s, const void *desc, const u32 *f, u32 m, u32 *park, u32 jobs, uint8_t *kind, uint8_t *pacc);
+extern "C" void lcbk_fe_pair_list(hipStream_t s, const uint8_t *kind, const uint8_t *pacc, u32 jobs, u32 *list, u32 *p2idx, u32 *cnt);
+extern "C" void lcbk_fe_pair_gather(hipStream_t s, const u32 *f, u32 m, const u32 *list, u32 n2, u32 *park2, uint8_t *pacc2);
+extern "C" void lcbk_fe_pair_finish(hipStream_t s, u32 *f, u32 m, u32 *park, u32 jobs, const uint8_t *kind, const uint8_t *pacc, const u32 *p2idx, const u32 *park2, u32 n2, uint8_t *gacc);
 extern "C" void lcbk_rlc_search(dim3 grid, hipStream_t s, const void *search, u32 o, u32 m, const u32 *gamma, const u32 *park, uint8_t *accept, void *next, u32 *next_count, const u32 *key_idx, u32 n_keys, const u32 *susp);
 extern "C" void lcbk_rlc_census_desc(hipStream_t s, const u32 *grp_idx, const u32 *key_idx, u32 m, u32 n_grp, u32 n_keys, void *desc, uint8_t *accept);
 extern "C" void lcbk_rlc_census_stats(hipStream_t s, const u32 *key_idx, u32 m, u32 n_keys, const uint8_t *cval, const uint8_t *accept, u32 *susp, u32 *count);

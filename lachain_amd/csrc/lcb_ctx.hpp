@@ -80,9 +80,11 @@ struct lcb_ctx {
     hipEvent_t ver_ev[3] = {};
     bool ver_ev_ready = false, ver_ran = false;
     // randomized batch verification (k_batch.hip): r_i U_i / r_i Y_i records, group lists, group points, counts
-    DevBuf rlc[20];                   // [12]: the keys' fixed-base tables, [13] suspect-key bitmap, [14] census validity,
+    DevBuf rlc[22];                   // [12]: the keys' fixed-base tables, [13] suspect-key bitmap, [14] census validity,
                                       // [15] coop Miller fallback flags, [16] TPKE level-2 gamma_c / gamma_t rows, [17] its open groups,
-                                      // [18] H's hash validity (split preparation, fork mode 3)
+                                      // [18] H's hash validity (split preparation, fork mode 3), [20] the level-1 pair
+                                      // stage's two park buffers (products + solos, then pass 2), [21] its job lists
+    uint32_t fe_pair[4] = {};         // last call's pair stage: pairs formed, pairs failed, exponentiations of pass 1 / 2
     hipEvent_t rlc_ev[3] = {};
     hipEvent_t rlc_lev_ev[4] = {};    // per level: before sum / Miller / final exp / resolve
     float rlc_ms[4] = {};             // accumulated over the levels of the last call: sums, Miller, final exp (+ resolve

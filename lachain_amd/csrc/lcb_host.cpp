@@ -1234,6 +1234,7 @@ struct RlcStats {
     uint32_t levels[8] = {};
     float ms[6] = {};
     uint32_t census[4] = {};
+    uint32_t fe_pair[4] = {};
 };
 thread_local RlcStats t_rlc_stats;
 // cnt: [0] current level's groups, [1] next level's, [2] search entries, [3] suspect keys, [4] level-1 entries after
@@ -1457,9 +1458,65 @@ void *search2b_dump(hipStream_t s, const char *stage, u32 ns, u32 no, const u32 
     }
     return buf;
 }
+// The level-1 pair stage of the TPKE batch check (k_tpke.hip "level-1 pair stage"): one final exponentiation per pair
+// of randomized groups instead of one per group.  lcb_set_fe_pair_min: chunks of at least this many entries take it;
+// 0 = never, UINT32_MAX (the default) = more entries than lcb_set_coop_max's value, the chunks that would otherwise
+// take the one-lane final-exponentiation kernel (smaller, latency-bound levels keep their single pass).
+std::atomic<uint32_t> g_fe_pair_min{UINT32_MAX};
+bool fe_pair_wanted(size_t m) {
+    const uint32_t v = g_fe_pair_min.load(), cm = g_coop_max.load();
+    if (v == 0 || m < 2) return false;
+    if (v != UINT32_MAX) return m >= v;
+    return cm != UINT32_MAX && m > cm;
+}
+// the final exponentiations of a chunk's m entries (f: their Miller values, gacc: their pre-flags) in two passes: the
+// products of the pairs and the other entries, then, after one read of the count, the first member of every pair that
+// failed; leaves gacc and the failed entries' rows of f as the single pass does.  Each pass runs on the kernel its own
+// count selects (lcb_set_coop_max's rule; DESIGN.md §17 has the measured alternative).
+struct FePairWs {                  // the job lists in rlc[21]: one allocation, the u32 arrays first
+    u32 *cnt, *list, *p2idx;       // cnt[4] (k_fe_pair_list), pass 2's jobs, each job's place among them
+    uint8_t *kind, *pacc, *pacc2;  // per job: its kind and pass 1's flag; per pass-2 entry: its flag
+    static size_t bytes(u32 jobs) { return 16 + (size_t)jobs * (4 + 4 + 1 + 1 + 1); }
+    explicit FePairWs(void *p, u32 jobs)
+        : cnt((u32 *)p), list(cnt + 4), p2idx(list + jobs), kind((uint8_t *)(p2idx + jobs)), pacc(kind + jobs),
+          pacc2(pacc + jobs) {}
+};
+bool rlc_fe_pairs(lcb_ctx *c, const uint8_t *desc, u32 *f, u32 m, uint8_t *gacc, hipStream_t s) {
+    const u32 jobs = (m + 1) / 2;
+    const size_t park_words = (size_t)jobs * 144 * (size_t)lcbk_fe_slots();
+    // pass 1's slots, then pass 2's: sized for the worst case (every job listed) so that no allocation follows the
+    // count's read
+    u32 *park = (u32 *)c->rlc[20].get(2 * park_words * 4);
+    void *lists = c->rlc[21].get(FePairWs::bytes(jobs));
+    if (!park || !lists) { set_err("device allocation failed (pair stage)"); return false; }
+    u32 *park2 = park + park_words;
+    const FePairWs ws(lists, jobs);
+    u32 *cnt = ws.cnt, *list = ws.list, *p2idx = ws.p2idx;
+    uint8_t *kind = ws.kind, *pacc = ws.pacc, *pacc2 = ws.pacc2;
+    hipMemsetAsync(cnt, 0, 16, s);
+    lcbk_fe_pair_pack(s, desc, f, m, park, jobs, kind, pacc);
+    if (jobs <= g_coop_max.load()) lcbk_coop_final_exp_check_2w(s, park, jobs, pacc);
+    else lcbk_final_exp_check(dim3(nblk(jobs)), s, park, jobs, pacc);
+    lcbk_fe_pair_list(s, kind, pacc, jobs, list, p2idx, cnt);
+    u32 h[3] = {0, 0, 0};
+    if (!launched("batched verify launch") || !read_counts(h, cnt, 3, s)) return false;
+    const u32 n2 = h[0];
+    if (n2 > jobs) { set_err("batched verify: pair stage count"); return false; }
+    if (n2) {
+        lcbk_fe_pair_gather(s, f, m, list, n2, park2, pacc2);
+        if (n2 <= g_coop_max.load()) lcbk_coop_final_exp_check_2w(s, park2, n2, pacc2);
+        else lcbk_final_exp_check(dim3(nblk(n2)), s, park2, n2, pacc2);
+    }
+    lcbk_fe_pair_finish(s, f, m, park, jobs, kind, pacc, p2idx, park2, n2, gacc);
+    c->fe_pair[0] += h[1];
+    c->fe_pair[1] += h[2];
+    c->fe_pair[2] += jobs;
+    c->fe_pair[3] += n2;
+    return true;
+}
 // Miller + final exponentiation (+ resolve / search) over the groups of desc in chunks; gpts holds the points
 enum RlcStage { RLC_RESOLVE = 0, RLC_SEARCH = 1, RLC_COPY = 2 };   // after a chunk's checks: resolve / search / copy out
-void rlc_checks(lcb_ctx *c, const RlcKindInfo &K, RlcWs &w, const uint8_t *desc, u32 count, void *gpts, uint8_t *gacc,
+bool rlc_checks(lcb_ctx *c, const RlcKindInfo &K, RlcWs &w, const uint8_t *desc, u32 count, void *gpts, uint8_t *gacc,
                 u32 *f, RlcStage stage, bool first, uint8_t *gex, uint4 *sdesc, u32 *gamma, uint8_t *d_accept,
                 RlcIo io, hipStream_t s, const u32 *copy_map = nullptr, bool census = false) {
     hipEvent_t *ev = c->rlc_lev_ev;
@@ -1470,6 +1527,7 @@ void rlc_checks(lcb_ctx *c, const RlcKindInfo &K, RlcWs &w, const uint8_t *desc,
         hipEventRecord(ev[1], s);
         // small levels (below one wave per SIMD as one check per lane): nine lanes per check (k_coop.hip)
         const bool coop = m <= g_coop_max.load(), coop_ml = m <= g_coop_miller_max.load();
+        const bool pairs = stage == RLC_RESOLVE && first && !K.ts && !census && fe_pair_wanted(m);
         if (tsc)
             lcbk_ts_rlc_miller_census(dim3(nblk(m)), s, K.lines, desc + 16 * o, (const uint8_t *)gpts + K.rec * o,
                                       (u32)m, f, gacc + o);
@@ -1485,7 +1543,9 @@ void rlc_checks(lcb_ctx *c, const RlcKindInfo &K, RlcWs &w, const uint8_t *desc,
         hipEventRecord(ev[2], s);
         // the nine-lane final exponentiation at 248 registers (k_prep.hip): it shares a SIMD with a randomisation wave
         // of the batches in flight (three TPKE batches: 15.50-15.78 vs 15.26-15.46 M/s, profiles/r05/abfe2w)
-        if (coop) lcbk_coop_final_exp_check_2w(s, f, (u32)m, gacc + o);
+        if (pairs) {                      // (the time of both passes, with the count's read between them)
+            if (!rlc_fe_pairs(c, desc + 16 * o, f, (u32)m, gacc + o, s)) return false;
+        } else if (coop) lcbk_coop_final_exp_check_2w(s, f, (u32)m, gacc + o);
         else lcbk_final_exp_check(dim3(nblk(m)), s, f, (u32)m, gacc + o);
         hipEventRecord(ev[3], s);
         if (stage == RLC_COPY)
@@ -1501,6 +1561,7 @@ void rlc_checks(lcb_ctx *c, const RlcKindInfo &K, RlcWs &w, const uint8_t *desc,
             if (hipEventElapsedTime(&t, ev[2], ev[3]) == hipSuccess) c->rlc_ms[2] += t;
         }
     }
+    return true;
 }
 // the census (SURVEY-style Byzantine validators, k_batch.hip "suspect keys"): exact single checks of shares [0, m),
 // then the suspect-key bitmap and its count (cnt[3]); everything stays on the device (no host read)
@@ -1531,6 +1592,7 @@ int rlc_levels(lcb_ctx *c, RlcKind kind, RlcWs &w, uint8_t *d_accept, size_t n, 
     RlcKindInfo K = rlc_kind(c, kind);
     u32 cnt[5] = {0, 0, 0, 0, 0};
     for (auto &m : c->rlc_ms) m = 0.0f;
+    for (auto &v : c->fe_pair) v = 0;
     if (!read_counts(cnt, w.cnt, 4, s)) return -1;
     if (!K.ts) K.fb = lines_unnormalised(c, 1) || (c->unn_census == 0 && lines_unnormalised(c, 0));
     u32 groups = cnt[0];
@@ -1573,7 +1635,8 @@ int rlc_levels(lcb_ctx *c, RlcKind kind, RlcWs &w, uint8_t *d_accept, size_t n, 
         hipEventRecord(ev[1], s);
         if (hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess)
             c->rlc_ms[0] += t;
-        rlc_checks(c, K, w, w.dA, groups, gpts, gacc, f, RLC_RESOLVE, first, gex, sdesc, gamma, d_accept, io, s);
+        if (!rlc_checks(c, K, w, w.dA, groups, gpts, gacc, f, RLC_RESOLVE, first, gex, sdesc, gamma, d_accept, io, s))
+            return -1;
         if (!launched("batched verify launch")) return -1;
         if (!read_counts(cnt, w.cnt, 3, s)) return -1;
         if (first && cnt[2] && !K.ts) {  // TPKE level 2: weighted re-check per failed group, one-error search, then
@@ -1664,6 +1727,7 @@ int rlc_levels(lcb_ctx *c, RlcKind kind, RlcWs &w, uint8_t *d_accept, size_t n, 
         if (!st.valid || hipEventElapsedTime(&st.ms[i], c->rlc_ev[i], c->rlc_ev[i + 1]) != hipSuccess) st.ms[i] = -1.0f;
     for (int i = 0; i < 4; i++) st.ms[2 + i] = c->rlc_ms[i];
     for (int i = 0; i < 4; i++) st.census[i] = c->rlc_census[i];
+    for (int i = 0; i < 4; i++) st.fe_pair[i] = c->fe_pair[i];
     return launched("batched verify launch") ? 0 : -1;
 }
 int tpke_verify_prepared_rlc(lcb_ctx *c, uint8_t *d_accept, size_t n, size_t n_keys, size_t n_cts, const uint32_t *d_ct,
@@ -2257,6 +2321,24 @@ extern "C" int lcb_set_coop_max(uint32_t max_checks) {
     if (!tuning_allowed("lcb_set_coop_max")) return -1;
     g_coop_max.store(max_checks);
     g_coop_miller_max.store(max_checks);
+    return 0;
+}
+extern "C" int lcb_set_fe_pair_min(uint32_t min_entries) {
+    if (!tuning_allowed("lcb_set_fe_pair_min")) return -1;
+    g_fe_pair_min.store(min_entries);
+    return 0;
+}
+extern "C" int lcb_ctx_tpke_fe_pair_stats(lcb_ctx *ctx, uint32_t out[4]) {
+    CTX_OR(c, ctx, -1)
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    if (!c->rlc_ran) { set_err("tpke batched verify: none has run in this context"); return -1; }
+    for (int i = 0; i < 4; i++) out[i] = c->fe_pair[i];
+    return 0;
+}
+extern "C" int lcb_tpke_fe_pair_stats(uint32_t out[4]) {
+    const RlcStats &st = t_rlc_stats;
+    if (!st.valid) { set_err("batched verify: none has completed on this thread"); return -1; }
+    for (int i = 0; i < 4; i++) out[i] = st.fe_pair[i];
     return 0;
 }
 extern "C" int lcb_set_verify_chunk(size_t checks) {

@@ -94,6 +94,9 @@ _SIGS = {
     "lcb_set_batch_seed": (None, [ctypes.c_char_p]),
     "lcb_set_batch_census": (None, [c_size]),
     "lcb_set_coop_max": (ctypes.c_int, [ctypes.c_uint32]),
+    "lcb_set_fe_pair_min": (ctypes.c_int, [ctypes.c_uint32]),
+    "lcb_tpke_fe_pair_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32)]),
+    "lcb_ctx_tpke_fe_pair_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
     "lcb_set_scratch_gate": (ctypes.c_int, [ctypes.c_longlong]),
     "lcb_scratch_gate_stats": (None, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "lcb_scratch_info": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
@@ -1032,6 +1035,23 @@ def set_verify_chunk(checks):
 def set_coop_max(max_checks):
     """levels of <= max_checks group checks use the nine-lane cooperative kernels (0 = never; default 32768)"""
     _tuning(lib().lcb_set_coop_max(max_checks), "set_coop_max")
+
+
+def set_fe_pair_min(min_entries=None):
+    """level-1 chunks of the TPKE batched check with >= min_entries entries run one final exponentiation per pair of
+    randomized groups (0 = never; None = the default: more entries than set_coop_max's value)"""
+    _tuning(lib().lcb_set_fe_pair_min(0xFFFFFFFF if min_entries is None else int(min_entries)), "set_fe_pair_min")
+
+
+def tpke_fe_pair_stats(ctx=None):
+    """[pairs formed, pairs failed, final exponentiations in pass 1, in pass 2] of the pair stage in this thread's
+    last batched verify (ctx: a Context, that context's last one)"""
+    out = (ctypes.c_uint32 * 4)()
+    if ctx is None:
+        _check(lib().lcb_tpke_fe_pair_stats(out), "tpke_fe_pair_stats")
+    else:
+        _check(lib().lcb_ctx_tpke_fe_pair_stats(ctx.ptr, out), "tpke_fe_pair_stats")
+    return list(out)
 
 
 def set_coop_miller_max(max_checks):
