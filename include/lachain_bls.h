@@ -347,6 +347,23 @@ int lcb_set_fe_pair_min(uint32_t min_entries);
 /* that stage in the calling thread's last batched verify (lcb_ctx_ form: that context's last one): {pairs formed,
    pairs that failed, final exponentiations run in pass 1, in pass 2}; all 0 when the stage did not run */
 int lcb_tpke_fe_pair_stats(uint32_t out[4]);
+/* The final exponentiation of a TPKE level when batches overlap.  The library counts, per device, the batched TPKE
+   verify calls (lcb_tpke_verify_shares_batched, its _dev and lcb_ctx_ forms) between entry and return.  A call that
+   sees at least one other call counted on its device when it enqueues a level's final exponentiation (a single pass,
+   either pass of the pair stage, any level) runs it on the nine-lane kernel only if the dispatch has at most
+   max_checks checks, otherwise on the one-lane kernel, which issues about a third fewer instructions per check; a
+   call that has the device to itself keeps lcb_set_coop_max's rule.  UINT32_MAX = the rule is off.  The Miller loops
+   (lcb_set_coop_miller_max), the pair stage's trigger (lcb_set_fe_pair_min), CommonCoin and the census are not
+   affected.  Keep it at 1024 or more: a one-lane final exponentiation takes about 12 ms however few checks it has,
+   and the aggregation queue's workers overlap each other with flushes of at most 64 shares.  Decisions are
+   unchanged.  Tuning hook (LCB_ALLOW_TUNING=1). */
+int lcb_set_busy_coop_max(uint32_t max_checks);
+uint32_t lcb_busy_coop_max(void);          /* the value in force */
+/* test / A-B switch of that rule: 0 = by the in-flight count (the default), 1 = never overlapped, 2 = always
+   overlapped (every batched TPKE level, the prepared forms included).  Tuning hook (LCB_ALLOW_TUNING=1). */
+int lcb_set_level_mode(int mode);
+/* batched TPKE verify calls now between entry and return on `device` (-1: device out of range) */
+int lcb_batched_inflight(int device);
 /* shares / group checks per Miller + final-exponentiation launch pair (default and maximum 2^21): a test hook that
    makes small batches run several chunks (chunk offsets in the copies and searches).  Set it only while no batch call
    is in flight.  Tuning hook (LCB_ALLOW_TUNING=1). */
@@ -433,6 +450,10 @@ int lcb_ctx_tpke_verify_shares_batched_dev(lcb_ctx *ctx, uint8_t *accept, size_t
 int lcb_ctx_tpke_batched_stats(lcb_ctx *ctx, uint32_t levels[8], float ms[6]);
 int lcb_ctx_batched_census(lcb_ctx *ctx, uint32_t out[4]);
 int lcb_ctx_tpke_fe_pair_stats(lcb_ctx *ctx, uint32_t out[4]);
+/* the level final exponentiations of the context's last batched verify (ctx NULL: the default context): {dispatches on
+   the one-lane kernel, on the nine-lane kernel, one-lane dispatches taken because the call was overlapped
+   (lcb_set_busy_coop_max), the largest in-flight count seen when a TPKE level chose}; the census is not counted */
+int lcb_ctx_tpke_level_kernel_stats(lcb_ctx *ctx, uint32_t out[4]);
 int lcb_ctx_ts_verify_prepared_batched_dev(lcb_ctx *ctx, uint8_t *accept, size_t n, size_t n_pks, size_t n_msgs,
                                            const uint8_t *sigs, const uint32_t *msg_idx, const uint32_t *pk_idx,
                                            void *stream);

@@ -85,6 +85,9 @@ struct lcb_ctx {
                                       // [18] H's hash validity (split preparation, fork mode 3), [20] the level-1 pair
                                       // stage's two park buffers (products + solos, then pass 2), [21] its job lists
     uint32_t fe_pair[4] = {};         // last call's pair stage: pairs formed, pairs failed, exponentiations of pass 1 / 2
+    uint32_t lvl_kernel[4] = {};      // last call's level final exponentiations: dispatches on the one-lane / nine-lane
+                                      // kernel, one-lane because the call was overlapped, largest in-flight count seen
+    bool lvl_counted = false;         // this call holds a count in the device's in-flight counter (BatchedInflight)
     hipEvent_t rlc_ev[3] = {};
     hipEvent_t rlc_lev_ev[4] = {};    // per level: before sum / Miller / final exp / resolve
     float rlc_ms[4] = {};             // accumulated over the levels of the last call: sums, Miller, final exp (+ resolve

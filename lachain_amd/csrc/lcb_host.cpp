@@ -1156,6 +1156,53 @@ std::atomic<int> g_fork_mode{4};            // lcb_set_fork_mode: stream layout 
 std::atomic<uint32_t> g_coop_max{32768};    // lcb_set_coop_max: batches / levels of <= this many checks use the 9-lane kernels
 std::atomic<uint32_t> g_coop_miller_max{65536};   // lcb_set_coop_miller_max: the same for the group Miller loops only
                                                   // (65536: level 1 too, 105.5 vs 106.1 ms, profiles/r03/ab2)
+// The kernel form of a TPKE level's final exponentiation when batches overlap.  The nine-lane kernel
+// issues about 50 % more wave instructions per check than the one-lane kernel; they buy latency while a level is below
+// one wave per SIMD and nothing while other batches keep the SIMDs full.  g_batched_inflight counts, per device, the
+// batched TPKE verify calls between entry and return; a call that sees another one counted when it enqueues a level's
+// final exponentiation is overlapped, and then lcb_set_busy_coop_max's value decides instead of lcb_set_coop_max's.
+// Default 20,000: pass 1 of the headline batch's pair stage (23.8 K jobs) moves, pass 2 and level 2 (8.5 K and 9.4 K
+// checks, under one one-lane wave per SIMD) stay: moving them too measured no better than moving nothing (§18).
+#ifndef LCB_BUSY_COOP_MAX
+#define LCB_BUSY_COOP_MAX 20000u
+#endif
+static_assert(LCB_BUSY_COOP_MAX >= 1024u, "the aggregation queue's overlapping small flushes keep the nine-lane kernel");
+std::atomic<uint32_t> g_busy_coop_max{LCB_BUSY_COOP_MAX};   // UINT32_MAX: the rule is off
+std::atomic<int> g_level_mode{0};                 // lcb_set_level_mode: 0 by the count, 1 never overlapped, 2 always
+std::atomic<uint32_t> g_batched_inflight[64];
+struct BatchedInflight {                          // scope guard: every return of the counted call releases its count
+    lcb_ctx *c;
+    std::atomic<uint32_t> *a;
+    explicit BatchedInflight(lcb_ctx *c_)
+        : c(c_), a(c_->device >= 0 && c_->device < 64 && !c_->lvl_counted ? &g_batched_inflight[c_->device] : nullptr) {
+        if (a) { a->fetch_add(1); c->lvl_counted = true; }
+    }
+    ~BatchedInflight() {
+        if (a) { c->lvl_counted = false; a->fetch_sub(1); }
+    }
+    BatchedInflight(const BatchedInflight &) = delete;
+    BatchedInflight &operator=(const BatchedInflight &) = delete;
+};
+// the kernel of a final-exponentiation dispatch of m checks in the level driver: true = one-lane.  ruled: a TPKE level
+// (not CommonCoin, not a census chain), where the overlap rule may replace lcb_set_coop_max's
+bool fe_one_lane(lcb_ctx *c, size_t m, bool ruled) {
+    const bool lat_one = m > g_coop_max.load();
+    bool one = lat_one;
+    const uint32_t bm = g_busy_coop_max.load();
+    if (ruled) {
+        const int mode = g_level_mode.load();
+        uint32_t nfl = 0;
+        if (c->device >= 0 && c->device < 64) nfl = g_batched_inflight[c->device].load();
+        if (nfl > c->lvl_kernel[3]) c->lvl_kernel[3] = nfl;
+        const bool busy = mode == 2 || (mode == 0 && c->lvl_counted && nfl >= 2);
+        if (busy && bm != UINT32_MAX) {
+            one = m > bm;
+            if (one && !lat_one) c->lvl_kernel[2]++;
+        }
+    }
+    c->lvl_kernel[one ? 0 : 1]++;
+    return one;
+}
 // the exact check of n shares against prepared line sets (lines, ctok: n_cts ciphertexts) and decompressed keys
 int tpke_verify_core(lcb_ctx *c, const u32 *lines, const uint8_t *ctok, size_t n_cts, const void *keys, size_t n_keys,
                      uint8_t *d_accept, size_t n, const uint32_t *d_ct, const uint32_t *d_dec, const uint8_t *d_ui,
@@ -1472,7 +1519,7 @@ bool fe_pair_wanted(size_t m) {
 // the final exponentiations of a chunk's m entries (f: their Miller values, gacc: their pre-flags) in two passes: the
 // products of the pairs and the other entries, then, after one read of the count, the first member of every pair that
 // failed; leaves gacc and the failed entries' rows of f as the single pass does.  Each pass runs on the kernel its own
-// count selects (lcb_set_coop_max's rule; DESIGN.md §17 has the measured alternative).
+// count selects (lcb_set_coop_max's rule, or lcb_set_busy_coop_max's when the call is overlapped: fe_one_lane).
 struct FePairWs {                  // the job lists in rlc[21]: one allocation, the u32 arrays first
     u32 *cnt, *list, *p2idx;       // cnt[4] (k_fe_pair_list), pass 2's jobs, each job's place among them
     uint8_t *kind, *pacc, *pacc2;  // per job: its kind and pass 1's flag; per pass-2 entry: its flag
@@ -1495,7 +1542,7 @@ bool rlc_fe_pairs(lcb_ctx *c, const uint8_t *desc, u32 *f, u32 m, uint8_t *gacc,
     uint8_t *kind = ws.kind, *pacc = ws.pacc, *pacc2 = ws.pacc2;
     hipMemsetAsync(cnt, 0, 16, s);
     lcbk_fe_pair_pack(s, desc, f, m, park, jobs, kind, pacc);
-    if (jobs <= g_coop_max.load()) lcbk_coop_final_exp_check_2w(s, park, jobs, pacc);
+    if (!fe_one_lane(c, jobs, true)) lcbk_coop_final_exp_check_2w(s, park, jobs, pacc);
     else lcbk_final_exp_check(dim3(nblk(jobs)), s, park, jobs, pacc);
     lcbk_fe_pair_list(s, kind, pacc, jobs, list, p2idx, cnt);
     u32 h[3] = {0, 0, 0};
@@ -1504,7 +1551,7 @@ bool rlc_fe_pairs(lcb_ctx *c, const uint8_t *desc, u32 *f, u32 m, uint8_t *gacc,
     if (n2 > jobs) { set_err("batched verify: pair stage count"); return false; }
     if (n2) {
         lcbk_fe_pair_gather(s, f, m, list, n2, park2, pacc2);
-        if (n2 <= g_coop_max.load()) lcbk_coop_final_exp_check_2w(s, park2, n2, pacc2);
+        if (!fe_one_lane(c, n2, true)) lcbk_coop_final_exp_check_2w(s, park2, n2, pacc2);
         else lcbk_final_exp_check(dim3(nblk(n2)), s, park2, n2, pacc2);
     }
     lcbk_fe_pair_finish(s, f, m, park, jobs, kind, pacc, p2idx, park2, n2, gacc);
@@ -1526,7 +1573,8 @@ bool rlc_checks(lcb_ctx *c, const RlcKindInfo &K, RlcWs &w, const uint8_t *desc,
         const size_t m = count - o < LCB_VERIFY_CHUNK ? count - o : LCB_VERIFY_CHUNK;
         hipEventRecord(ev[1], s);
         // small levels (below one wave per SIMD as one check per lane): nine lanes per check (k_coop.hip)
-        const bool coop = m <= g_coop_max.load(), coop_ml = m <= g_coop_miller_max.load();
+        // (the final exponentiation's form also depends on the batches in flight: fe_one_lane)
+        const bool coop_ml = m <= g_coop_miller_max.load();
         const bool pairs = stage == RLC_RESOLVE && first && !K.ts && !census && fe_pair_wanted(m);
         if (tsc)
             lcbk_ts_rlc_miller_census(dim3(nblk(m)), s, K.lines, desc + 16 * o, (const uint8_t *)gpts + K.rec * o,
@@ -1545,7 +1593,7 @@ bool rlc_checks(lcb_ctx *c, const RlcKindInfo &K, RlcWs &w, const uint8_t *desc,
         // of the batches in flight (three TPKE batches: 15.50-15.78 vs 15.26-15.46 M/s, profiles/r05/abfe2w)
         if (pairs) {                      // (the time of both passes, with the count's read between them)
             if (!rlc_fe_pairs(c, desc + 16 * o, f, (u32)m, gacc + o, s)) return false;
-        } else if (coop) lcbk_coop_final_exp_check_2w(s, f, (u32)m, gacc + o);
+        } else if (!fe_one_lane(c, m, !K.ts && !census)) lcbk_coop_final_exp_check_2w(s, f, (u32)m, gacc + o);
         else lcbk_final_exp_check(dim3(nblk(m)), s, f, (u32)m, gacc + o);
         hipEventRecord(ev[3], s);
         if (stage == RLC_COPY)
@@ -1593,6 +1641,7 @@ int rlc_levels(lcb_ctx *c, RlcKind kind, RlcWs &w, uint8_t *d_accept, size_t n, 
     u32 cnt[5] = {0, 0, 0, 0, 0};
     for (auto &m : c->rlc_ms) m = 0.0f;
     for (auto &v : c->fe_pair) v = 0;
+    for (auto &v : c->lvl_kernel) v = 0;
     if (!read_counts(cnt, w.cnt, 4, s)) return -1;
     if (!K.ts) K.fb = lines_unnormalised(c, 1) || (c->unn_census == 0 && lines_unnormalised(c, 0));
     u32 groups = cnt[0];
@@ -1782,6 +1831,7 @@ int tpke_verify_shares_rlc_fused(lcb_ctx *c, uint8_t *d_accept, size_t n, const 
                                  const uint8_t *d_u, const uint8_t *d_w, const uint8_t *d_v, const uint32_t *d_voff,
                                  size_t n_cts, const uint32_t *d_ct, const uint32_t *d_dec, const uint8_t *d_ui,
                                  hipStream_t s) {
+    const BatchedInflight counted(c);          // until this call returns: the level driver's overlap rule (fe_one_lane)
     if (n_cts > 0xffffffffu || n_keys > 0xffffffffu || n > 0xffffffffu) { set_err("tpke batched verify: batch too large"); return -1; }
     c->t_ready = false;
     c->unn_set[0] = c->unn_set[1] = false;     // the fallback flags describe the line sets prepared below
@@ -2326,6 +2376,29 @@ extern "C" int lcb_set_coop_max(uint32_t max_checks) {
 extern "C" int lcb_set_fe_pair_min(uint32_t min_entries) {
     if (!tuning_allowed("lcb_set_fe_pair_min")) return -1;
     g_fe_pair_min.store(min_entries);
+    return 0;
+}
+extern "C" int lcb_set_busy_coop_max(uint32_t max_checks) {
+    if (!tuning_allowed("lcb_set_busy_coop_max")) return -1;
+    g_busy_coop_max.store(max_checks);
+    return 0;
+}
+extern "C" uint32_t lcb_busy_coop_max(void) { return g_busy_coop_max.load(); }
+extern "C" int lcb_set_level_mode(int mode) {
+    if (!tuning_allowed("lcb_set_level_mode")) return -1;
+    if (mode < 0 || mode > 2) { set_err("lcb_set_level_mode: 0 (by the count), 1 (never busy), 2 (always busy)"); return -1; }
+    g_level_mode.store(mode);
+    return 0;
+}
+extern "C" int lcb_batched_inflight(int device) {
+    if (device < 0 || device >= 64) { set_err("lcb_batched_inflight: device out of range"); return -1; }
+    return (int)g_batched_inflight[device].load();
+}
+extern "C" int lcb_ctx_tpke_level_kernel_stats(lcb_ctx *ctx, uint32_t out[4]) {
+    CTX_OR(c, ctx, -1)
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    if (!c->rlc_ran) { set_err("tpke batched verify: none has run in this context"); return -1; }
+    for (int i = 0; i < 4; i++) out[i] = c->lvl_kernel[i];
     return 0;
 }
 extern "C" int lcb_ctx_tpke_fe_pair_stats(lcb_ctx *ctx, uint32_t out[4]) {

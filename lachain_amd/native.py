@@ -96,6 +96,11 @@ _SIGS = {
     "lcb_set_coop_max": (ctypes.c_int, [ctypes.c_uint32]),
     "lcb_set_fe_pair_min": (ctypes.c_int, [ctypes.c_uint32]),
     "lcb_tpke_fe_pair_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32)]),
+    "lcb_set_busy_coop_max": (ctypes.c_int, [ctypes.c_uint32]),
+    "lcb_busy_coop_max": (ctypes.c_uint32, []),
+    "lcb_set_level_mode": (ctypes.c_int, [ctypes.c_int]),
+    "lcb_batched_inflight": (ctypes.c_int, [ctypes.c_int]),
+    "lcb_ctx_tpke_level_kernel_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
     "lcb_ctx_tpke_fe_pair_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
     "lcb_set_scratch_gate": (ctypes.c_int, [ctypes.c_longlong]),
     "lcb_scratch_gate_stats": (None, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
@@ -1051,6 +1056,36 @@ def tpke_fe_pair_stats(ctx=None):
         _check(lib().lcb_tpke_fe_pair_stats(out), "tpke_fe_pair_stats")
     else:
         _check(lib().lcb_ctx_tpke_fe_pair_stats(ctx.ptr, out), "tpke_fe_pair_stats")
+    return list(out)
+
+
+def set_busy_coop_max(max_checks):
+    """a batched TPKE verify that overlaps another one on its device runs a level's final exponentiation on the
+    nine-lane kernel only up to max_checks checks, above that on the one-lane kernel (0xFFFFFFFF = the rule is off)"""
+    _tuning(lib().lcb_set_busy_coop_max(int(max_checks)), "set_busy_coop_max")
+
+
+def busy_coop_max():
+    """the value in force (the library's default until set_busy_coop_max changes it)"""
+    return int(lib().lcb_busy_coop_max())
+
+
+def set_level_mode(mode):
+    """the overlap rule of set_busy_coop_max: 0 = by the in-flight count, 1 = never overlapped, 2 = always"""
+    _tuning(lib().lcb_set_level_mode(int(mode)), "set_level_mode")
+
+
+def batched_inflight(device=0):
+    """batched TPKE verify calls between entry and return on `device`"""
+    return int(lib().lcb_batched_inflight(int(device)))
+
+
+def tpke_level_kernel_stats(ctx=None):
+    """[final-exponentiation dispatches on the one-lane kernel, on the nine-lane kernel, one-lane dispatches taken
+    because the call was overlapped, largest in-flight count seen] of the levels of the last batched TPKE verify in
+    ctx (None: the default context)"""
+    out = (ctypes.c_uint32 * 4)()
+    _check(lib().lcb_ctx_tpke_level_kernel_stats(None if ctx is None else ctx.ptr, out), "tpke_level_kernel_stats")
     return list(out)
 
 
