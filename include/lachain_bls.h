@@ -674,6 +674,75 @@ int lcb_keccak256_batch(uint8_t *out32, const uint8_t *data, const uint64_t *off
 int lcb_ctx_keccak256_dev(lcb_ctx *ctx, uint8_t *out32, const uint8_t *data, const uint64_t *off, size_t n, void *stream);
 int lcb_keccak256_dev(uint8_t *out32, const uint8_t *data, const uint64_t *off, size_t n, void *stream);
 
+/* ------------------------------------------------------------------ secp256k1 ECIES (the trustless DKG's envelopes)
+   Every secret of the trustless key generation travels in DefaultCrypto.Secp256K1Encrypt and is opened by
+   Secp256K1Decrypt (DefaultCrypto.cs:301-336): StartKeygen wraps one row per validator, HandleCommit opens a row and
+   wraps N values, HandleSendValue opens a value (TrustlessKeygen.cs:63-76,90-109,111-135).  An envelope is
+     eph_pub33 || nonce16 || C || tag16,   key = Secp256K1.Ecdh = SHA-256(compressed d P)
+   (libsecp256k1's secp256k1_ecdh with its default hash), AES-256-GCM as BouncyCastle's GcmBlockCipher(AesEngine) with
+   a 16-byte nonce, no associated data and a 16-byte tag (AesGcmEncrypt / AesGcmDecrypt, DefaultCrypto.cs:267-299; the
+   nonce is not 96 bits, so J0 = GHASH(nonce || 0^64 || [128]_64), NIST SP 800-38D).  Kernels: k_ecies.hip.
+   Items are given as in lcb_keccak256_batch: item i is the bytes [off[i], off[i + 1]) of its array, off has n + 1
+   non-decreasing entries.  Where the reference throws — a malformed or off-curve key (the 33-byte slot takes the
+   prefixes 0x02 and 0x03 only), a scalar outside [1, n), an envelope shorter than 65 bytes or a GCM item shorter than
+   32, a tag mismatch — the item gets ok[i] = 0 and zero output bytes and its neighbours are unaffected; only bad
+   arguments (a null pointer, a decreasing offset) fail the call.  n = 0 is a successful no-op.
+   The ephemeral private keys and the nonces come from the caller, as the signing entry points take their nonces: the
+   caller MUST draw both from a cryptographically secure generator and use each once.  A repeated (key, nonce) pair
+   gives away the GCM authentication key and the xor of the plaintexts.
+   No constant-time claim is made on the GPU (table lookups and skipped zero digits depend on the scalar): the
+   standing of lcb_ecdsa_sign_hashed_batch, lcb_ts_sign and lcb_tpke_partial_decrypt.  Workspaces and staging copies
+   that held private, ephemeral or session keys are cleared on the stream before a call returns. */
+/* key32_out[i] = SHA-256 of the compressed d P (Secp256K1.Ecdh); ok[i] = 0 and zero bytes where libsecp256k1 returns
+   0.  Item i uses scalars32[scalar_idx[i]] (an index >= n_scalars fails the item), or scalars32[i] when scalar_idx is
+   null (n_scalars is then ignored) */
+int lcb_secp_ecdh_batch(uint8_t *key32_out, uint8_t *ok, const uint8_t *pub33, const uint8_t *scalars32,
+                        const uint32_t *scalar_idx, size_t n_scalars, size_t n);
+/* AesGcmEncrypt with caller-given nonces: out item i = nonce || C || tag at out + (pt_off[i] - pt_off[0]) + 32 i */
+int lcb_aes256_gcm_encrypt_batch(uint8_t *out, const uint8_t *keys32, const uint8_t *nonces16, const uint8_t *pt,
+                                 const uint64_t *pt_off, size_t n);
+/* AesGcmDecrypt: the plaintexts are packed in item order, item i after the plaintexts of the items before it (a
+   rejected item of valid length keeps its zeroed slot, an item shorter than 32 bytes takes none): at ct_off[i] -
+   ct_off[0] - 32 i when no item is too short.  pt_out holds at most ct_off[n] - ct_off[0] bytes */
+int lcb_aes256_gcm_decrypt_batch(uint8_t *pt_out, uint8_t *ok, const uint8_t *keys32, const uint8_t *ct,
+                                 const uint64_t *ct_off, size_t n);
+/* Secp256K1Encrypt: out item i = eph_pub33 || nonce || C || tag, 65 bytes longer than its plaintext, at
+   out + (pt_off[i] - pt_off[0]) + 65 i; the ephemeral public key is eph_priv32[i] G */
+int lcb_secp256k1_encrypt_batch(uint8_t *out, uint8_t *ok, const uint8_t *recipient_pub33, const uint8_t *eph_priv32,
+                                const uint8_t *nonces16, const uint8_t *pt, const uint64_t *pt_off, size_t n);
+/* Secp256K1Decrypt: item i is opened with privs32[priv_idx[i]], or privs32[i] when priv_idx is null; the plaintexts
+   are packed as by lcb_aes256_gcm_decrypt_batch with 65 bytes of overhead per item */
+int lcb_secp256k1_decrypt_batch(uint8_t *pt_out, uint8_t *ok, const uint8_t *privs32, const uint32_t *priv_idx,
+                                size_t n_privs, const uint8_t *ct, const uint64_t *ct_off, size_t n);
+/* device-pointer forms on a stream (asynchronous), with and without an explicit context.  They trust the offsets
+   (which are absolute into pt / ct; the output positions are as above) */
+int lcb_ctx_secp_ecdh_dev(lcb_ctx *ctx, uint8_t *key32_out, uint8_t *ok, const uint8_t *pub33, const uint8_t *scalars32,
+                          const uint32_t *scalar_idx, size_t n_scalars, size_t n, void *stream);
+int lcb_ctx_aes256_gcm_encrypt_dev(lcb_ctx *ctx, uint8_t *out, const uint8_t *keys32, const uint8_t *nonces16,
+                                   const uint8_t *pt, const uint64_t *pt_off, size_t n, void *stream);
+int lcb_ctx_aes256_gcm_decrypt_dev(lcb_ctx *ctx, uint8_t *pt_out, uint8_t *ok, const uint8_t *keys32, const uint8_t *ct,
+                                   const uint64_t *ct_off, size_t n, void *stream);
+int lcb_ctx_secp256k1_encrypt_dev(lcb_ctx *ctx, uint8_t *out, uint8_t *ok, const uint8_t *recipient_pub33,
+                                  const uint8_t *eph_priv32, const uint8_t *nonces16, const uint8_t *pt,
+                                  const uint64_t *pt_off, size_t n, void *stream);
+int lcb_ctx_secp256k1_decrypt_dev(lcb_ctx *ctx, uint8_t *pt_out, uint8_t *ok, const uint8_t *privs32,
+                                  const uint32_t *priv_idx, size_t n_privs, const uint8_t *ct, const uint64_t *ct_off,
+                                  size_t n, void *stream);
+int lcb_secp_ecdh_dev(uint8_t *key32_out, uint8_t *ok, const uint8_t *pub33, const uint8_t *scalars32,
+                      const uint32_t *scalar_idx, size_t n_scalars, size_t n, void *stream);
+int lcb_aes256_gcm_encrypt_dev(uint8_t *out, const uint8_t *keys32, const uint8_t *nonces16, const uint8_t *pt,
+                               const uint64_t *pt_off, size_t n, void *stream);
+int lcb_aes256_gcm_decrypt_dev(uint8_t *pt_out, uint8_t *ok, const uint8_t *keys32, const uint8_t *ct,
+                               const uint64_t *ct_off, size_t n, void *stream);
+int lcb_secp256k1_encrypt_dev(uint8_t *out, uint8_t *ok, const uint8_t *recipient_pub33, const uint8_t *eph_priv32,
+                              const uint8_t *nonces16, const uint8_t *pt, const uint64_t *pt_off, size_t n, void *stream);
+int lcb_secp256k1_decrypt_dev(uint8_t *pt_out, uint8_t *ok, const uint8_t *privs32, const uint32_t *priv_idx,
+                              size_t n_privs, const uint8_t *ct, const uint64_t *ct_off, size_t n, void *stream);
+/* kernel milliseconds of the last ECIES call in the context: scalars, multiplication, finish, GCM (with the
+   ephemeral public keys of an encryption); a phase the call did not run reads 0 */
+int lcb_ctx_ecies_phase_ms(lcb_ctx *ctx, float ms[4]);
+int lcb_ecies_phase_ms(float ms[4]);
+
 /* ------------------------------------------------------------------ aggregation queue (one share per call)
    The consensus code verifies one share per call from many protocol threads (HoneyBadger.cs:156-158,211-212,
    ThresholdSigner.cs:62, AbstractProtocol.cs:46-47).  A queue aggregates such calls into GPU batches: submit

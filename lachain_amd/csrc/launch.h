@@ -101,6 +101,14 @@ extern "C" void lcbk_secp_rec_scalars(hipStream_t s, const uint8_t *hashes, cons
 extern "C" void lcbk_secp_recover(hipStream_t s, const void *jobs, u32 n, const void *g_table, void *pts);
 extern "C" void lcbk_secp_rec_finish(hipStream_t s, const void *pts, u32 n, uint8_t *pub33, uint8_t *addr20, uint8_t *ok, const uint8_t *from20, uint8_t *accept);
 extern "C" void lcbk_keccak256(hipStream_t s, const uint8_t *data, const uint64_t *off, u32 n, uint8_t *out32);
+extern "C" size_t lcbk_ecdh_job_bytes(void);
+extern "C" size_t lcbk_ecdh_point_bytes(void);
+extern "C" void lcbk_ecdh_scalars(hipStream_t s, const uint8_t *pub, const uint64_t *off, u32 min_len, const uint8_t *scalars32, const u32 *idx, u32 n_scalars, u32 n, void *jobs);
+extern "C" void lcbk_ecdh_mul(hipStream_t s, const void *jobs, u32 n, void *pts);
+extern "C" void lcbk_ecdh_finish(hipStream_t s, const void *pts, u32 n, uint8_t *key32, uint8_t *ok);
+extern "C" void lcbk_gcm_offsets(hipStream_t s, const uint64_t *off, u32 n, u32 overhead, uint64_t *out_off);
+extern "C" void lcbk_gcm_encrypt(hipStream_t s, const uint8_t *keys32, const uint8_t *nonces16, const uint8_t *pt, const uint64_t *pt_off, u32 n, uint8_t *out, const uint8_t *hdr33, const uint8_t *ok_in);
+extern "C" void lcbk_gcm_decrypt(hipStream_t s, const uint8_t *keys32, const uint8_t *ct, const uint64_t *ct_off, const uint64_t *out_off, u32 n, u32 hdr, uint8_t *pt_out, uint8_t *ok_out, const uint8_t *ok_in);
 extern "C" size_t lcbk_key_table_bytes(u32 n_keys);
 extern "C" void lcbk_rlc_key_tables(dim3 grid, hipStream_t s, const void *keys, u32 n_keys, u32 *ws, u32 **tab, uint8_t **ktab_ok);
 extern "C" void lcbk_tpke_rlc_points(hipStream_t s, u32 n_cts, const void *keys, u32 n_keys, const u32 *ct_idx, const u32 *dec_idx, const uint8_t *ui, u32 i0, u32 n, const u32 key[10], u32 *rU, u32 *rY, uint8_t *accept, const u32 *ktab, const uint8_t *ktab_ok, const u32 *susp);

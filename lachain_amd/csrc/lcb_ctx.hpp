@@ -128,6 +128,11 @@ struct lcb_ctx {
     bool er_ev_ready = false, er_ran = false;
     // reliable-broadcast Merkle layer and block roots (lcb_rbc.cpp): staging, offsets, RS positions / matrices, trees
     DevBuf rbc[12];
+    // secp256k1 ECIES (lcb_ecies.cpp): [0] job records, [1] Jacobian results, [2] session keys, [3] ECDH validity,
+    // [4] ephemeral public keys, [5] their validity, [6] plaintext offsets, [7..13] staging of the host-pointer forms
+    DevBuf ecies[14];
+    hipEvent_t ecies_ev[5] = {};      // around scalars / multiplication / finish / GCM of the last call
+    bool ecies_ev_ready = false, ecies_ran = false;
 };
 
 // Enqueue scope: exclusive use of the context, stream ordered after the context's previous work, and the

@@ -1015,6 +1015,7 @@ void ctx_free(lcb_ctx *c) {
         for (auto &e : c->prep_ev) (void)hipEventDestroy(e);
     }
     lcb_int::ecdsa_ctx_release(c);
+    lcb_int::ecies_ctx_release(c);
     if (c->ver_ev_ready) for (auto &e : c->ver_ev) (void)hipEventDestroy(e);
     if (c->msm_ev_ready) for (auto &e : c->msm_ev) (void)hipEventDestroy(e);
     if (c->order) (void)hipEventDestroy(c->order);

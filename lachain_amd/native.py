@@ -219,6 +219,18 @@ _SIGS = {
     "lcb_ecdsa_recover_phase_ms": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float)]),
     "lcb_keccak256_batch": (ctypes.c_int, [c_u8p, c_u8p, ctypes.POINTER(ctypes.c_uint64), c_size]),
     "lcb_keccak256_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_size, ctypes.c_void_p]),
+    "lcb_secp_ecdh_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u32p, c_size, c_size]),
+    "lcb_aes256_gcm_encrypt_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u64p, c_size]),
+    "lcb_aes256_gcm_decrypt_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u64p, c_size]),
+    "lcb_secp256k1_encrypt_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u64p, c_size]),
+    "lcb_secp256k1_decrypt_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u32p, c_size, c_u8p, c_u64p, c_size]),
+    "lcb_secp_ecdh_dev": (ctypes.c_int, [ctypes.c_void_p] * 5 + [c_size, c_size, ctypes.c_void_p]),
+    "lcb_aes256_gcm_encrypt_dev": (ctypes.c_int, [ctypes.c_void_p] * 5 + [c_size, ctypes.c_void_p]),
+    "lcb_aes256_gcm_decrypt_dev": (ctypes.c_int, [ctypes.c_void_p] * 5 + [c_size, ctypes.c_void_p]),
+    "lcb_secp256k1_encrypt_dev": (ctypes.c_int, [ctypes.c_void_p] * 7 + [c_size, ctypes.c_void_p]),
+    "lcb_secp256k1_decrypt_dev": (ctypes.c_int, [ctypes.c_void_p] * 4 + [c_size, ctypes.c_void_p, ctypes.c_void_p,
+                                                                         c_size, ctypes.c_void_p]),
+    "lcb_ecies_phase_ms": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float)]),
     "lcb_rbc_shard_size": (c_size, [c_size, ctypes.c_int, ctypes.c_int]),
     "lcb_rbc_tree_depth": (ctypes.c_int, [ctypes.c_int]),
     "lcb_rbc_val_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u64p, c_size, ctypes.c_int, ctypes.c_int]),
@@ -243,7 +255,8 @@ for _name in ("tpke_prepare_dev", "tpke_verify_prepared_dev", "tpke_verify_prepa
               "root_header_verify_dev", "ecdsa_pubkey_dev", "ecdsa_sign_hashed_dev", "ecdsa_phase_ms", "batched_census",
               "tpke_combine_ordered_dev", "ts_assemble_ordered_dev", "ecdsa_recover_hashed_dev",
               "ecdsa_special_recover_hashed_dev", "tx_verify_dev", "ecdsa_recover_phase_ms", "keccak256_dev",
-              "rbc_check_echo_dev", "rbc_merkle_tree_dev", "merkle_root_dev"):
+              "rbc_check_echo_dev", "rbc_merkle_tree_dev", "merkle_root_dev", "secp_ecdh_dev", "aes256_gcm_encrypt_dev",
+              "aes256_gcm_decrypt_dev", "secp256k1_encrypt_dev", "secp256k1_decrypt_dev", "ecies_phase_ms"):
     _res, _args = _SIGS["lcb_" + _name]
     _SIGS["lcb_ctx_" + _name] = (_res, [ctypes.c_void_p] + list(_args))
 
@@ -698,6 +711,100 @@ def keccak256_batch(msgs) -> bytes:
     ob, po = _out(32 * n)
     _check(lib().lcb_keccak256_batch(po, pd, offs, n), "keccak256_batch")
     return bytes(ob)[: 32 * n]
+
+
+# ---------------------------------------------------------------- secp256k1 ECIES (the trustless DKG's envelopes)
+def _packed(ob, lens, ok):
+    """the packed outputs of a decryption: one bytes object per accepted item, None where ok is 0"""
+    out, pos = [], 0
+    for ln, good in zip(lens, ok):
+        out.append(bytes(ob[pos:pos + ln]) if good else None)
+        pos += ln
+    return out
+
+
+def secp_ecdh_batch(pubs33: bytes, scalars32: bytes, scalar_idx=None):
+    """Secp256K1.Ecdh over a batch: (32-byte keys, ok); item i uses scalar scalar_idx[i], or scalar i without an index.
+    Where libsecp256k1 returns 0, ok is 0 and the key bytes are zero"""
+    n = len(pubs33) // 33
+    keep = []
+    _, pp = _bytes_ptr_keep(keep, pubs33)
+    _, ps = _bytes_ptr_keep(keep, scalars32)
+    pi = _u32_keep(keep, scalar_idx)[1] if scalar_idx is not None else None
+    kb, pk = _out(32 * n)
+    okb, pok = _out(n)
+    _check(lib().lcb_secp_ecdh_batch(pk, pok, pp, ps, pi, len(scalars32) // 32, n), "secp_ecdh_batch")
+    return bytes(kb)[: 32 * n], bytes(okb)[:n]
+
+
+def aes256_gcm_encrypt_batch(keys32: bytes, nonces16: bytes, pts):
+    """AesGcmEncrypt with the given nonces: the list of nonce || C || tag"""
+    n = len(pts)
+    off = _offsets(pts)
+    keep = []
+    _, pk = _bytes_ptr_keep(keep, keys32)
+    _, pn = _bytes_ptr_keep(keep, nonces16)
+    _, pd = _bytes_ptr_keep(keep, b"".join(pts))
+    ob, po = _out(off[-1] + 32 * n)
+    _check(lib().lcb_aes256_gcm_encrypt_batch(po, pk, pn, pd, _u64_keep(keep, off), n), "aes256_gcm_encrypt_batch")
+    raw = bytes(ob)
+    return [raw[off[i] + 32 * i: off[i + 1] + 32 * (i + 1)] for i in range(n)]
+
+
+def aes256_gcm_decrypt_batch(keys32: bytes, items):
+    """AesGcmDecrypt: (plaintexts, ok); a rejected item (too short, tag mismatch) is None"""
+    n = len(items)
+    off = _offsets(items)
+    keep = []
+    _, pk = _bytes_ptr_keep(keep, keys32)
+    _, pd = _bytes_ptr_keep(keep, b"".join(items))
+    ob, po = _out(off[-1])
+    okb, pok = _out(n)
+    _check(lib().lcb_aes256_gcm_decrypt_batch(po, pok, pk, pd, _u64_keep(keep, off), n), "aes256_gcm_decrypt_batch")
+    ok = bytes(okb)[:n]
+    return _packed(bytes(ob), [max(len(c) - 32, 0) for c in items], ok), ok
+
+
+def secp256k1_encrypt_batch(recipient_pubs33: bytes, eph_privs32: bytes, nonces16: bytes, pts):
+    """Secp256K1Encrypt with the given ephemeral keys and nonces (both must come from a CSPRNG, each used once):
+    (envelopes eph_pub33 || nonce || C || tag, ok); an item whose key or scalar is invalid is None"""
+    n = len(pts)
+    off = _offsets(pts)
+    keep = []
+    _, pr = _bytes_ptr_keep(keep, recipient_pubs33)
+    _, pe = _bytes_ptr_keep(keep, eph_privs32)
+    _, pn = _bytes_ptr_keep(keep, nonces16)
+    _, pd = _bytes_ptr_keep(keep, b"".join(pts))
+    ob, po = _out(off[-1] + 65 * n)
+    okb, pok = _out(n)
+    _check(lib().lcb_secp256k1_encrypt_batch(po, pok, pr, pe, pn, pd, _u64_keep(keep, off), n),
+           "secp256k1_encrypt_batch")
+    raw, ok = bytes(ob), bytes(okb)[:n]
+    return [raw[off[i] + 65 * i: off[i + 1] + 65 * (i + 1)] if ok[i] else None for i in range(n)], ok
+
+
+def secp256k1_decrypt_batch(privs32: bytes, envelopes, priv_idx=None):
+    """Secp256K1Decrypt: (plaintexts, ok); envelope i is opened with key priv_idx[i], or key i without an index; None
+    where the reference throws"""
+    n = len(envelopes)
+    off = _offsets(envelopes)
+    keep = []
+    _, pp = _bytes_ptr_keep(keep, privs32)
+    pi = _u32_keep(keep, priv_idx)[1] if priv_idx is not None else None
+    _, pd = _bytes_ptr_keep(keep, b"".join(envelopes))
+    ob, po = _out(off[-1])
+    okb, pok = _out(n)
+    _check(lib().lcb_secp256k1_decrypt_batch(po, pok, pp, pi, len(privs32) // 32, pd, _u64_keep(keep, off), n),
+           "secp256k1_decrypt_batch")
+    ok = bytes(okb)[:n]
+    return _packed(bytes(ob), [max(len(c) - 65, 0) for c in envelopes], ok), ok
+
+
+def ecies_phase_ms():
+    """kernel milliseconds of the calling thread's last ECIES call: [scalars, multiplication, finish, GCM]"""
+    ms = (ctypes.c_float * 4)()
+    _check(lib().lcb_ecies_phase_ms(ms), "ecies_phase_ms")
+    return list(ms)
 
 
 # ---------------------------------------------------------------- reliable broadcast: Merkle layer (§8f row 3)
