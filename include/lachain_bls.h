@@ -644,8 +644,9 @@ int lcb_ecdsa_recover_hashed_batch(uint8_t *pub33_out, uint8_t *addr20_out, uint
 int lcb_ecdsa_special_recover_hashed_batch(uint8_t *pub33_out, uint8_t *addr20_out, uint8_t *ok, const uint8_t *hashes,
                                            const uint8_t *sigs, size_t sig_len, size_t n);
 /* The cache-miss branch of TransactionVerifier.VerifyTransactionImmediately (TransactionVerifier.cs:124-130):
-   accept[i] = the signature recovers and the recovered address equals from20[i].  The receipt.Hash == FullHash check
-   (line 115) stays with the caller.  The reference's cached-key branch is VerifySignatureHashed
+   accept[i] = the signature recovers and the recovered address equals from20[i], on hashes the caller already holds.
+   lcb_receipts_verify_batch (below) is the whole method from the receipt's fields: it computes RawHash and FullHash on
+   the device and includes the receipt.Hash == FullHash check (line 115).  The reference's cached-key branch is VerifySignatureHashed
    (lcb_ecdsa_verify_hashed_batch), which enforces low s; this branch does not, exactly as in the reference. */
 int lcb_tx_verify_batch(uint8_t *accept, const uint8_t *hashes, const uint8_t *sigs, size_t sig_len,
                         const uint8_t *from20, size_t n, int use_new_chain_id, int32_t chain_id);
@@ -673,6 +674,78 @@ int lcb_ecdsa_recover_phase_ms(float ms[3]);
 int lcb_keccak256_batch(uint8_t *out32, const uint8_t *data, const uint64_t *off, size_t n);
 int lcb_ctx_keccak256_dev(lcb_ctx *ctx, uint8_t *out32, const uint8_t *data, const uint64_t *off, size_t n, void *stream);
 int lcb_keccak256_dev(uint8_t *out32, const uint8_t *data, const uint64_t *off, size_t n, void *stream);
+
+/* ------------------------------------------------------------------ transaction hashing and receipt verification
+   A receipt goes in as fields; its RLP is formed and hashed on the device (k_txhash.hip), exactly as
+   TransactionUtils.GetEthTx / Rlp / RlpWithSignature / RawHash / FullHash produce it (TransactionUtils.cs:30-105,
+   HexUtils.cs:88-92, Nethereum RLP.EncodeElement / EncodeList):
+     RawHash  = Keccak-256(list[nonce, gasPrice, gasLimit, to, value, invocation, chainId, "", ""])
+     FullHash = Keccak-256(list[nonce, gasPrice, gasLimit, to, value, invocation, v, r, s])
+   nonce is the empty string when 0, otherwise minimal big-endian; gasPrice, gasLimit and chainId are minimal
+   big-endian with zero as the one byte 00; to is its 20 bytes or the empty string; value is its 32 bytes with leading
+   zero bytes stripped (nothing left for zero); r = sig[0:32] and s = sig[32:64] likewise; v = sig[64:sig_len] with
+   leading zeros stripped unless it is all zero, when it stays whole (00, or 82 00 00 for two bytes).  These rules
+   reproduce the five strings and four hashes of CryptographyTest.cs:208-274, the zero-signature encoding of system
+   transactions among them.  A signature with only one of r, s zero is pinned by no reference vector; the same rule is
+   applied to it (such a signature never recovers).
+   Item i: txs[i], invocation bytes invocations[inv_off[i] .. inv_off[i + 1]) (inv_off has n + 1 entries), signature
+   sigs + sig_len * i, claimed hash hashes32 + 32 * i.  sig_len must be 65 for the old chain id and 66 for the new one;
+   `chain_id` is TransactionUtils.ChainId(use_new_chain_id).  A call fails (-1) for a missing pointer, a wrong sig_len, a
+   negative chain id and, in the host-pointer forms, for decreasing offsets, an invocation of 2^31 bytes or more and a
+   to_len other than 0 or 20; the device-pointer forms cannot read their inputs and trust the caller for these three
+   (txs and inv_off 8-byte aligned).  A bad item never fails a call. */
+typedef struct {
+    uint64_t nonce, gas_price, gas_limit;
+    uint8_t value[32];          /* UInt256 buffer, big-endian */
+    uint8_t to[20];
+    uint8_t from[20];           /* Transaction.From: read by the receipt calls only */
+    uint32_t to_len;            /* 20, or 0 for an empty To */
+    uint32_t reserved;          /* 0 */
+} lcb_tx_fields;                /* 104 bytes */
+/* raw32_out / full32_out: n x 32 bytes, each may be null; with sigs == NULL only raw32_out is written */
+int lcb_tx_hash_batch(uint8_t *raw32_out, uint8_t *full32_out, const lcb_tx_fields *txs, const uint8_t *invocations,
+                      const uint64_t *inv_off, const uint8_t *sigs, size_t sig_len, size_t n, int use_new_chain_id,
+                      int32_t chain_id);
+int lcb_ctx_tx_hash_dev(lcb_ctx *ctx, uint8_t *raw32_out, uint8_t *full32_out, const lcb_tx_fields *txs,
+                        const uint8_t *invocations, const uint64_t *inv_off, const uint8_t *sigs, size_t sig_len, size_t n,
+                        int use_new_chain_id, int32_t chain_id, void *stream);
+int lcb_tx_hash_dev(uint8_t *raw32_out, uint8_t *full32_out, const lcb_tx_fields *txs, const uint8_t *invocations,
+                    const uint64_t *inv_off, const uint8_t *sigs, size_t sig_len, size_t n, int use_new_chain_id,
+                    int32_t chain_id, void *stream);
+/* TransactionVerifier.VerifyTransactionImmediately(receipt, useNewChainId, cacheEnabled: false)
+   (TransactionVerifier.cs:109-143) per item, in one call: hashing, the hash check, the recovery (the rules of
+   lcb_ecdsa_recover_hashed_batch: no low-s rule) and the From comparison all run on the device and the raw hashes
+   never leave it.  detail[i] bit 0: hashes32[i] == FullHash; bit 1: the signature recovers from RawHash; bit 2: the
+   recovered address equals txs[i].from.  accept[i] = (detail[i] == 7); detail may be null.  Nothing throws. */
+int lcb_receipts_verify_batch(uint8_t *accept, uint8_t *detail, const lcb_tx_fields *txs, const uint8_t *invocations,
+                              const uint64_t *inv_off, const uint8_t *sigs, size_t sig_len, const uint8_t *hashes32,
+                              size_t n, int use_new_chain_id, int32_t chain_id);
+int lcb_ctx_receipts_verify_dev(lcb_ctx *ctx, uint8_t *accept, uint8_t *detail, const lcb_tx_fields *txs,
+                                const uint8_t *invocations, const uint64_t *inv_off, const uint8_t *sigs, size_t sig_len,
+                                const uint8_t *hashes32, size_t n, int use_new_chain_id, int32_t chain_id, void *stream);
+int lcb_receipts_verify_dev(uint8_t *accept, uint8_t *detail, const lcb_tx_fields *txs, const uint8_t *invocations,
+                            const uint64_t *inv_off, const uint8_t *sigs, size_t sig_len, const uint8_t *hashes32, size_t n,
+                            int use_new_chain_id, int32_t chain_id, void *stream);
+/* The same for the receipts of n_blocks blocks: block b holds receipts tx_off[b] .. tx_off[b + 1] (tx_off runs from 0 to
+   n), and root_ok[b] = (MerkleTree.ComputeRoot(the given hashes of block b) ?? Zero) == expected_roots[b]
+   (BlockManager.cs:690-694; lcb_merkle_root_batch's tree).  A block without transactions gives root_ok = (expected is
+   all zero). */
+int lcb_block_txs_verify_batch(uint8_t *accept, uint8_t *detail, uint8_t *root_ok, const lcb_tx_fields *txs,
+                               const uint8_t *invocations, const uint64_t *inv_off, const uint8_t *sigs, size_t sig_len,
+                               const uint8_t *hashes32, size_t n, const uint64_t *tx_off, const uint8_t *expected_roots,
+                               size_t n_blocks, int use_new_chain_id, int32_t chain_id);
+int lcb_ctx_block_txs_verify_dev(lcb_ctx *ctx, uint8_t *accept, uint8_t *detail, uint8_t *root_ok, const lcb_tx_fields *txs,
+                                 const uint8_t *invocations, const uint64_t *inv_off, const uint8_t *sigs, size_t sig_len,
+                                 const uint8_t *hashes32, size_t n, const uint64_t *tx_off, const uint8_t *expected_roots,
+                                 size_t n_blocks, int use_new_chain_id, int32_t chain_id, void *stream);
+int lcb_block_txs_verify_dev(uint8_t *accept, uint8_t *detail, uint8_t *root_ok, const lcb_tx_fields *txs,
+                             const uint8_t *invocations, const uint64_t *inv_off, const uint8_t *sigs, size_t sig_len,
+                             const uint8_t *hashes32, size_t n, const uint64_t *tx_off, const uint8_t *expected_roots,
+                             size_t n_blocks, int use_new_chain_id, int32_t chain_id, void *stream);
+/* kernel milliseconds of the last transaction call enqueued in the context (the *_dev forms; NULL = the calling thread's
+   default context): hashing, recovery with the decision, roots */
+int lcb_ctx_tx_phase_ms(lcb_ctx *ctx, float ms[3]);
+int lcb_tx_phase_ms(float ms[3]);
 
 /* ------------------------------------------------------------------ secp256k1 ECIES (the trustless DKG's envelopes)
    Every secret of the trustless key generation travels in DefaultCrypto.Secp256K1Encrypt and is opened by

@@ -101,6 +101,9 @@ extern "C" void lcbk_secp_rec_scalars(hipStream_t s, const uint8_t *hashes, cons
 extern "C" void lcbk_secp_recover(hipStream_t s, const void *jobs, u32 n, const void *g_table, void *pts);
 extern "C" void lcbk_secp_rec_finish(hipStream_t s, const void *pts, u32 n, uint8_t *pub33, uint8_t *addr20, uint8_t *ok, const uint8_t *from20, uint8_t *accept);
 extern "C" void lcbk_keccak256(hipStream_t s, const uint8_t *data, const uint64_t *off, u32 n, uint8_t *out32);
+extern "C" void lcbk_tx_hash(hipStream_t s, const uint8_t *txs, const uint8_t *inv, const uint64_t *off, const uint8_t *sigs, u32 sig_len, const uint8_t *claimed, u32 chain_id, u32 n, uint8_t *raw32, uint8_t *full32, uint8_t *match, uint32_t *long_ws);
+extern "C" void lcbk_tx_detail(hipStream_t s, const uint8_t *match, const uint8_t *rec_ok, const uint8_t *addr20, const uint8_t *txs, u32 n, uint8_t *accept, uint8_t *detail);
+extern "C" void lcbk_tx_root_ok(hipStream_t s, const uint8_t *roots, const uint8_t *expected, u32 n, uint8_t *root_ok);
 extern "C" size_t lcbk_ecdh_job_bytes(void);
 extern "C" size_t lcbk_ecdh_point_bytes(void);
 extern "C" void lcbk_ecdh_scalars(hipStream_t s, const uint8_t *pub, const uint64_t *off, u32 min_len, const uint8_t *scalars32, const u32 *idx, u32 n_scalars, u32 n, void *jobs);

@@ -133,6 +133,12 @@ struct lcb_ctx {
     DevBuf ecies[14];
     hipEvent_t ecies_ev[5] = {};      // around scalars / multiplication / finish / GCM of the last call
     bool ecies_ev_ready = false, ecies_ran = false;
+    // transaction hashing and receipt verification (lcb_txhash.cpp): [0] raw hashes, [1] hash-match / recovered flags,
+    // [2] recovered addresses, [3] block roots and their status, [4..11] staging of the host-pointer forms, [12] the
+    // count and list of long items that k_tx_hash leaves to k_tx_hash_long
+    DevBuf tx[13];
+    hipEvent_t tx_ev[4] = {};         // around hashing / recovery and decision / roots of the last call
+    bool tx_ev_ready = false, tx_ran = false;
 };
 
 // Enqueue scope: exclusive use of the context, stream ordered after the context's previous work, and the

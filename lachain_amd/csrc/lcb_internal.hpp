@@ -13,4 +13,5 @@ bool sync_ok(lcb_ctx *c, const char *what);
 int device();
 void ecdsa_ctx_release(lcb_ctx *c);   // lcb_ecdsa.cpp: the context's cached key set
 void ecies_ctx_release(lcb_ctx *c);   // lcb_ecies.cpp: the envelope workspaces and events
+void txhash_ctx_release(lcb_ctx *c);  // lcb_txhash.cpp: the transaction workspaces and events
 }  // namespace lcb_int

@@ -5,6 +5,7 @@ library is missing or no gfx950 device can be opened, `lib()` raises.
 """
 import ctypes
 import os
+import struct
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -243,6 +244,20 @@ _SIGS = {
                                             c_u8p, c_size, ctypes.c_int, ctypes.c_int]),
     "lcb_merkle_root_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u64p, c_size]),
     "lcb_merkle_root_dev": (ctypes.c_int, [ctypes.c_void_p] * 4 + [c_size, c_size, ctypes.c_void_p]),
+    "lcb_tx_hash_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u64p, c_u8p, c_size, c_size, ctypes.c_int,
+                                         ctypes.c_int32]),
+    "lcb_tx_hash_dev": (ctypes.c_int, [ctypes.c_void_p] * 6 + [c_size, c_size, ctypes.c_int, ctypes.c_int32,
+                                                               ctypes.c_void_p]),
+    "lcb_receipts_verify_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u64p, c_u8p, c_size, c_u8p, c_size,
+                                                 ctypes.c_int, ctypes.c_int32]),
+    "lcb_receipts_verify_dev": (ctypes.c_int, [ctypes.c_void_p] * 6 + [c_size, ctypes.c_void_p, c_size, ctypes.c_int,
+                                                                       ctypes.c_int32, ctypes.c_void_p]),
+    "lcb_block_txs_verify_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u64p, c_u8p, c_size, c_u8p,
+                                                  c_size, c_u64p, c_u8p, c_size, ctypes.c_int, ctypes.c_int32]),
+    "lcb_block_txs_verify_dev": (ctypes.c_int, [ctypes.c_void_p] * 7 + [c_size, ctypes.c_void_p, c_size,
+                                                                        ctypes.c_void_p, ctypes.c_void_p, c_size,
+                                                                        ctypes.c_int, ctypes.c_int32, ctypes.c_void_p]),
+    "lcb_tx_phase_ms": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float)]),
     "lcb_ctx_create": (ctypes.c_void_p, []),
     "lcb_ctx_destroy": (None, [ctypes.c_void_p]),
     "lcb_ctx_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
@@ -256,7 +271,8 @@ for _name in ("tpke_prepare_dev", "tpke_verify_prepared_dev", "tpke_verify_prepa
               "tpke_combine_ordered_dev", "ts_assemble_ordered_dev", "ecdsa_recover_hashed_dev",
               "ecdsa_special_recover_hashed_dev", "tx_verify_dev", "ecdsa_recover_phase_ms", "keccak256_dev",
               "rbc_check_echo_dev", "rbc_merkle_tree_dev", "merkle_root_dev", "secp_ecdh_dev", "aes256_gcm_encrypt_dev",
-              "aes256_gcm_decrypt_dev", "secp256k1_encrypt_dev", "secp256k1_decrypt_dev", "ecies_phase_ms"):
+              "aes256_gcm_decrypt_dev", "secp256k1_encrypt_dev", "secp256k1_decrypt_dev", "ecies_phase_ms", "tx_hash_dev",
+              "receipts_verify_dev", "block_txs_verify_dev", "tx_phase_ms"):
     _res, _args = _SIGS["lcb_" + _name]
     _SIGS["lcb_ctx_" + _name] = (_res, [ctypes.c_void_p] + list(_args))
 
@@ -711,6 +727,84 @@ def keccak256_batch(msgs) -> bytes:
     ob, po = _out(32 * n)
     _check(lib().lcb_keccak256_batch(po, pd, offs, n), "keccak256_batch")
     return bytes(ob)[: 32 * n]
+
+
+# ---------------------------------------------------------------- transaction hashing and receipt verification
+TX_FIELDS_BYTES = 104
+
+
+def tx_fields(nonce: int, gas_price: int, gas_limit: int, to: bytes, value32: bytes, from20: bytes = bytes(20)) -> bytes:
+    """lcb_tx_fields record (104 B): u64 nonce | gas_price | gas_limit | value[32] | to[20] | from[20] | u32 to_len | 0"""
+    if len(to) not in (0, 20) or len(value32) != 32 or len(from20) != 20:
+        raise ValueError("To is 20 bytes or empty, Value 32 bytes, From 20 bytes")
+    return struct.pack("<QQQ32s20s20sII", nonce, gas_price, gas_limit, value32, to.ljust(20, b"\0"), from20, len(to), 0)
+
+
+def _tx_inputs(keep, records: bytes, invocations):
+    n = len(records) // TX_FIELDS_BYTES
+    if len(invocations) != n:
+        raise ValueError("one invocation per record")
+    off = [0]
+    for inv in invocations:
+        off.append(off[-1] + len(inv))
+    _, pt = _bytes_ptr_keep(keep, records)
+    _, pi = _bytes_ptr_keep(keep, b"".join(invocations))
+    return n, pt, pi, _u64_keep(keep, off)
+
+
+def tx_hash_batch(records: bytes, invocations, sigs, sig_len: int, use_new_chain_id: bool, chain_id: int):
+    """(RawHash bytes, FullHash bytes) of n transactions given as lcb_tx_fields records and invocation byte strings;
+    sigs (n x sig_len bytes) may be None: FullHash is then None"""
+    keep = []
+    n, pt, pi, po = _tx_inputs(keep, records, invocations)
+    ps = None
+    if sigs is not None:
+        _, ps = _bytes_ptr_keep(keep, sigs)
+    rb, pr = _out(32 * n)
+    fb, pf = _out(32 * n)
+    _check(lib().lcb_tx_hash_batch(pr, pf if sigs is not None else None, pt, pi, po, ps, sig_len, n,
+                                   int(bool(use_new_chain_id)), chain_id), "tx_hash_batch")
+    return bytes(rb)[: 32 * n], (bytes(fb)[: 32 * n] if sigs is not None else None)
+
+
+def receipts_verify_batch(records: bytes, invocations, sigs: bytes, sig_len: int, hashes: bytes, use_new_chain_id: bool,
+                          chain_id: int):
+    """VerifyTransactionImmediately(receipt, useNewChainId, cacheEnabled: false) per receipt: (accept, detail) bytes;
+    detail bit 0 = Hash == FullHash, bit 1 = the signature recovers, bit 2 = the address is From"""
+    keep = []
+    n, pt, pi, po = _tx_inputs(keep, records, invocations)
+    _, ps = _bytes_ptr_keep(keep, sigs)
+    _, ph = _bytes_ptr_keep(keep, hashes)
+    ab, pa = _out(n)
+    db, pd = _out(n)
+    _check(lib().lcb_receipts_verify_batch(pa, pd, pt, pi, po, ps, sig_len, ph, n, int(bool(use_new_chain_id)), chain_id),
+           "receipts_verify_batch")
+    return bytes(ab)[:n], bytes(db)[:n]
+
+
+def block_txs_verify_batch(records: bytes, invocations, sigs: bytes, sig_len: int, hashes: bytes, tx_off,
+                           expected_roots: bytes, use_new_chain_id: bool, chain_id: int):
+    """receipts_verify_batch over the receipts of len(tx_off) - 1 blocks, and per block whether the Merkle root of its
+    given hashes (zero for an empty block) is the expected one: (accept, detail, root_ok) bytes"""
+    keep = []
+    n, pt, pi, po = _tx_inputs(keep, records, invocations)
+    B = len(tx_off) - 1
+    _, ps = _bytes_ptr_keep(keep, sigs)
+    _, ph = _bytes_ptr_keep(keep, hashes)
+    _, pe = _bytes_ptr_keep(keep, expected_roots)
+    ab, pa = _out(n)
+    db, pd = _out(n)
+    rb, pr = _out(B)
+    _check(lib().lcb_block_txs_verify_batch(pa, pd, pr, pt, pi, po, ps, sig_len, ph, n, _u64_keep(keep, tx_off), pe, B,
+                                            int(bool(use_new_chain_id)), chain_id), "block_txs_verify_batch")
+    return bytes(ab)[:n], bytes(db)[:n], bytes(rb)[:B]
+
+
+def tx_phase_ms():
+    """kernel milliseconds of the calling thread's last transaction call: [hashing, recovery and decision, roots]"""
+    ms = (ctypes.c_float * 3)()
+    _check(lib().lcb_tx_phase_ms(ms), "tx_phase_ms")
+    return list(ms)
 
 
 # ---------------------------------------------------------------- secp256k1 ECIES (the trustless DKG's envelopes)
