@@ -413,6 +413,15 @@ int lcb_debug_final_exp(const uint32_t *in, size_t n, uint32_t *out, int coop);
    4..6 Frobenius 1..3, 7 inverse, 8 conjugate, 9 sparse line product, 10 final exponentiation) on n values a (and b),
    with the one-lane field.hpp result beside it in ref */
 int lcb_debug_coop_op(int op, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out, uint32_t *ref);
+/* test hook: one routine of the assembly tower on n (1..65536) arbitrary Fp12 operands a (and b), same layout.
+   op & 255: 0 a b, 1 conj(a) b, 2 one Granger-Scott squaring, 3 a run of op >> 8 (1..255) squarings in one call,
+   4 a^z (z < 0 the curve parameter; a unitary).  b is read by ops 0 and 1 only. */
+int lcb_debug_asm_tower(int op, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out);
+/* test hook: lcb_tpke_verify_shares up to its Miller loop (the one-lane kernel) for n (1..65536) shares, without the
+   final exponentiation: f_out = each share's Miller value (144 x u32), ok_out = its validity flag */
+int lcb_debug_tpke_miller(uint32_t *f_out, uint8_t *ok_out, size_t n, const uint8_t *y_keys, size_t n_keys,
+                          const uint8_t *cts_u, const uint8_t *cts_w, const uint8_t *v_data, const uint32_t *v_off,
+                          size_t n_cts, const uint32_t *ct_idx, const uint32_t *dec_idx, const uint8_t *ui);
 
 /* ------------------------------------------------------------------ explicit execution contexts
    A context owns the device workspaces of the prepare/verify, assembly, Lagrange and MSM calls below

@@ -136,6 +136,22 @@ extern "C" __global__ void LCB_PAIR_BOUNDS k_final_exp_check(u32 *park, u32 n, u
     accept[i] = accept[i] && fp12_is_one(f);
 }
 
+// ---------------------------------------------------------------- test hook: the assembly tower on arbitrary operands
+// (lcb_debug_asm_tower).  park: four SoA slots of n items, a in slot 0, b in slot 1, the result in slot 2, slot 3 the
+// products' working space.  op: 0 fx_mul(a, b), 1 fx_mul(conj a, b), 2 one lcb_asm_cyc_sqr_n, 3 one call of `count`
+// squarings, 4 fx_pow_z(a).  The same per-lane 36 LDS quads and the same early exit of the lanes past n as
+// k_final_exp_check; op and count are uniform over the launch.
+extern "C" __global__ void LCB_PAIR_BOUNDS k_asm_tower_debug(int op, u32 *park, u32 n, u32 count) {
+    __shared__ uint4 fx_lds[36 * LCB_BLOCK];
+    const u32 lds = lane_lds36(fx_lds);
+    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u32 *A = park, *B = park + (size_t)144 * n, *D = park + (size_t)288 * n, *W = park + (size_t)432 * n;
+    if (op == 0 || op == 1) fx_mul(D, A, B, op, n, i, lds);
+    else if (op == 2 || op == 3) lcb_asm_cyc_sqr_n(A, D, n * 16, i * 16, op == 2 ? 1u : count);
+    else fx_pow_z(D, A, W, n, i, lds);
+}
+
 // TPKE.PrivateKey.Decrypt (TPKE/PrivateKey.cs:21-31): validity e(G, W) == e(U, H) <=> e(-G, W) e(U, H) == 1, then
 // Ui = x U.  Three launches over ciphertexts c0 + [0, m) (round 5; one fused kernel spilled 7.7 KB of scratch per lane):
 // the Miller loop parks f (SoA, as k_tpke_miller), k_final_exp_check ANDs f^((p^12-1)/r) == 1 into status, and the
@@ -230,6 +246,9 @@ extern "C" void lcbk_tpke_miller(dim3 grid, hipStream_t s, const u32 *lines, con
 }
 extern "C" void lcbk_final_exp_check(dim3 grid, hipStream_t s, u32 *park, u32 n, uint8_t *accept) {
     LCB_LAUNCH(k_final_exp_check, park, n, accept);
+}
+extern "C" void lcbk_asm_tower_debug(dim3 grid, hipStream_t s, int op, u32 *park, u32 n, u32 count) {
+    LCB_LAUNCH(k_asm_tower_debug, op, park, n, count);
 }
 extern "C" void lcbk_tpke_pd_miller(hipStream_t s, const u32 *lines, const uint8_t *ct_ok, const uint8_t *cts_u, u32 c0, u32 m, u32 *f_soa, uint8_t *status) {
     dim3 grid((m + LCB_BLOCK - 1) / LCB_BLOCK);

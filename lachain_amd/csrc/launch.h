@@ -22,6 +22,9 @@ extern "C" void lcbk_lineset_coop_2w(hipStream_t s, u32 *lines, u32 n_sets, cons
 extern "C" void lcbk_tpke_miller(dim3 grid, hipStream_t s, const u32 *lines, const uint8_t *ct_ok, u32 n_cts, const void *keys, u32 n_keys, const u32 *ct_idx, const u32 *dec_idx, const uint8_t *ui, u32 n, u32 *f_soa, uint8_t *accept);
 extern "C" int lcbk_fe_slots();
 extern "C" void lcbk_final_exp_check(dim3 grid, hipStream_t s, u32 *park, u32 n, uint8_t *accept);
+// test hook (lcb_debug_asm_tower): one assembly tower routine on n operands; park = 4 SoA slots of n items (a, b, result,
+// working space)
+extern "C" void lcbk_asm_tower_debug(dim3 grid, hipStream_t s, int op, u32 *park, u32 n, u32 count);
 // TPKE partial decryption over ciphertexts c0 + [0, m): Miller loop into f_soa (m x 576 B x lcbk_fe_slots()), then
 // lcbk_final_exp_check(f_soa, m, status + c0), then the ladder
 extern "C" void lcbk_tpke_pd_miller(hipStream_t s, const u32 *lines, const uint8_t *ct_ok, const uint8_t *cts_u, u32 c0, u32 m, u32 *f_soa, uint8_t *status);

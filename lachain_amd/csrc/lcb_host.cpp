@@ -2552,6 +2552,71 @@ extern "C" int lcb_debug_final_exp(const uint32_t *in, size_t n, uint32_t *out, 
         for (int w = 0; w < 144; w++) out[144 * i + w] = soa[((size_t)(w >> 2) * n + i) * 4 + (w & 3)];
     return 0;
 }
+// one assembly tower routine (asm_tower.hpp through fe_asm.hpp's wrappers, k_asm_tower_debug) on n operands, AoS in /
+// out as above.  op & 255: 0 a b, 1 conj(a) b (lcb_r_fp12_mul_n), 2 one Granger-Scott squaring, 3 op >> 8 (1..255)
+// squarings in one call (lcb_r_cyc_sqr_n), 4 a^z (lcb_r_pow_z); b is read by ops 0 and 1 only
+extern "C" int lcb_debug_asm_tower(int op, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out) {
+    SYNC_CTX_OR(c, -1)
+    Enq q(c, c->stream);
+    const int what = op & 255, count = op >> 8;
+    if (!n || n > 65536) { set_err("debug asm tower: 1..65536 values"); return -1; }
+    if (op < 0 || what > 4 || (what == 3 ? count < 1 || count > 255 : count != 0)) {
+        set_err("debug asm tower: op 0..4, a run length of 1..255 above bit 8 for op 3 only");
+        return -1;
+    }
+    if (what < 2 && !b) { set_err("debug asm tower: the product needs b"); return -1; }
+    const size_t W = (size_t)144 * n;
+    std::vector<u32> soa(W * 4, 0);
+    for (size_t i = 0; i < n; i++)
+        for (int w = 0; w < 144; w++) {
+            soa[((size_t)(w >> 2) * n + i) * 4 + (w & 3)] = a[144 * i + w];
+            if (what < 2) soa[W + ((size_t)(w >> 2) * n + i) * 4 + (w & 3)] = b[144 * i + w];
+        }
+    u32 *d = (u32 *)c->out[0].get(soa.size() * 4);
+    if (!d) { set_err("device allocation failed"); return -1; }
+    hipMemcpyAsync(d, soa.data(), soa.size() * 4, hipMemcpyHostToDevice, q.s);
+    lcbk_asm_tower_debug(dim3(nblk(n)), q.s, what, d, (u32)n, (u32)(count ? count : 1));
+    hipMemcpyAsync(soa.data(), d + 2 * W, W * 4, hipMemcpyDeviceToHost, q.s);
+    if (!sync_check(c, "debug asm tower")) return -1;
+    for (size_t i = 0; i < n; i++)
+        for (int w = 0; w < 144; w++) out[144 * i + w] = soa[((size_t)(w >> 2) * n + i) * 4 + (w & 3)];
+    return 0;
+}
+// the exact per-share check up to its Miller loop: lcb_tpke_verify_shares's uploads and prepare, then k_tpke_miller (the
+// one-lane kernel, whatever lcb_set_coop_max says) and no final exponentiation.  f_out: each share's parked Miller value
+// (slot 0, 144 words, AoS); ok_out: its validity flag (index range, decompression, key, ciphertext)
+extern "C" int lcb_debug_tpke_miller(uint32_t *f_out, uint8_t *ok_out, size_t n, const uint8_t *y_keys, size_t n_keys,
+                                     const uint8_t *cts_u, const uint8_t *cts_w, const uint8_t *v_data,
+                                     const uint32_t *v_off, size_t n_cts, const uint32_t *ct_idx,
+                                     const uint32_t *dec_idx, const uint8_t *ui) {
+    SYNC_CTX_OR(c, -1)
+    if (!n || n > 65536 || !n_cts || !n_keys) { set_err("debug tpke miller: 1..65536 shares, some keys and ciphertexts"); return -1; }
+    for (size_t i = 0; i < n; i++)
+        if (ct_idx[i] >= n_cts || dec_idx[i] >= n_keys) { set_err("debug tpke miller: index out of range"); return -1; }
+    Enq q(c, c->stream);
+    hipStream_t s = c->stream;
+    const uint8_t *dy = up(c->in[0], y_keys, 48 * n_keys, s);
+    const uint8_t *du = up(c->in[1], cts_u, 48 * n_cts, s);
+    const uint8_t *dw = up(c->in[2], cts_w, 96 * n_cts, s);
+    const uint8_t *dv = up(c->in[3], v_data, (size_t)v_off[n_cts], s);
+    const uint32_t *dvo = up(c->in[4], v_off, n_cts + 1, s);
+    const uint32_t *dct = up(c->in[5], ct_idx, n, s);
+    const uint32_t *ddec = up(c->in[6], dec_idx, n, s);
+    const uint8_t *dui = up(c->in[7], ui, 48 * n, s);
+    uint8_t *dacc = (uint8_t *)c->out[0].get(n);
+    u32 *f = (u32 *)c->t_f.get(n * 576 * (size_t)lcbk_fe_slots());
+    if (!dy || !du || !dw || !dv || !dvo || !dct || !ddec || !dui || !dacc || !f) { set_err("device allocation failed"); return -1; }
+    if (tpke_prepare(c, dy, n_keys, du, dw, dv, dvo, n_cts, s)) return -1;
+    lcbk_tpke_miller(dim3(nblk(n)), s, (const u32 *)c->t_lines.p, (const uint8_t *)c->t_ctok.p, (u32)n_cts, c->t_keys.p,
+                     (u32)n_keys, dct, ddec, dui, (u32)n, f, dacc);
+    std::vector<u32> soa((size_t)144 * n);
+    hipMemcpyAsync(soa.data(), f, soa.size() * 4, hipMemcpyDeviceToHost, s);
+    hipMemcpyAsync(ok_out, dacc, n, hipMemcpyDeviceToHost, s);
+    if (!sync_check(c, "debug tpke miller")) return -1;
+    for (size_t i = 0; i < n; i++)
+        for (int w = 0; w < 144; w++) f_out[144 * i + w] = soa[((size_t)(w >> 2) * n + i) * 4 + (w & 3)];
+    return 0;
+}
 extern "C" int lcb_ctx_batched_census(lcb_ctx *ctx, uint32_t out[4]) {
     CTX_OR(c, ctx, -1)
     std::lock_guard<std::recursive_mutex> lk(c->mu);

@@ -114,6 +114,10 @@ _SIGS = {
                                          c_size, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     "lcb_debug_final_exp": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32), c_size, ctypes.POINTER(ctypes.c_uint32),
                                            ctypes.c_int]),
+    "lcb_debug_asm_tower": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_uint32),
+                                           ctypes.POINTER(ctypes.c_uint32), c_size, ctypes.POINTER(ctypes.c_uint32)]),
+    "lcb_debug_tpke_miller": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32), c_u8p, c_size, c_u8p, c_size, c_u8p, c_u8p,
+                                             c_u8p, c_u32p, c_size, c_u32p, c_u32p, c_u8p]),
     "lcb_batched_census": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32)]),
     "lcb_tpke_partial_decrypt": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u32p, c_size]),
     "lcb_tpke_encrypt_phase1": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_size]),
@@ -1322,6 +1326,43 @@ def debug_coop_op(op, a_values, b_values):
     ref = (ctypes.c_uint32 * (144 * n))()
     _check(lib().lcb_debug_coop_op(op, a, b, n, out, ref), "debug_coop_op")
     return ([list(out[144 * i:144 * i + 144]) for i in range(n)], [list(ref[144 * i:144 * i + 144]) for i in range(n)])
+
+
+ASM_TOWER_OPS = {"mul": 0, "mul_conj": 1, "cyc_sqr": 2, "cyc_sqr_run": 3, "pow_z": 4}
+
+
+def debug_asm_tower(op, a_values, b_values=None, run=1):
+    """one routine of the assembly tower (lcb_debug_asm_tower; op: a key of ASM_TOWER_OPS, run: the number of
+    squarings of "cyc_sqr_run") on 144-word Fp12 values -> the 144-word results"""
+    code = ASM_TOWER_OPS[op]
+    if code == 3:
+        code |= run << 8
+    n = len(a_values)
+    a = (ctypes.c_uint32 * (144 * n))(*[w for v in a_values for w in v])
+    b = None if b_values is None else (ctypes.c_uint32 * (144 * n))(*[w for v in b_values for w in v])
+    out = (ctypes.c_uint32 * (144 * n))()
+    _check(lib().lcb_debug_asm_tower(code, a, b, n, out), "debug_asm_tower")
+    return [list(out[144 * i:144 * i + 144]) for i in range(n)]
+
+
+def debug_tpke_miller(y_keys, cts, shares):
+    """tpke_verify_shares's arguments -> [(Miller value as 144 words, validity flag)] per share: the exact check's
+    prepare and one-lane Miller kernel, without the final exponentiation (lcb_debug_tpke_miller)"""
+    n = len(shares)
+    keep = []
+    _, py = _bytes_ptr_keep(keep, b"".join(y_keys))
+    _, pu = _bytes_ptr_keep(keep, b"".join(c[0] for c in cts))
+    _, pw = _bytes_ptr_keep(keep, b"".join(c[2] for c in cts))
+    _, pv = _bytes_ptr_keep(keep, b"".join(c[1] for c in cts))
+    _, pvo = _u32_keep(keep, _offsets([c[1] for c in cts]))
+    _, pct = _u32_keep(keep, [s[0] for s in shares])
+    _, pdec = _u32_keep(keep, [s[1] for s in shares])
+    _, pui = _bytes_ptr_keep(keep, b"".join(s[2] for s in shares))
+    f = (ctypes.c_uint32 * (144 * max(1, n)))()
+    ob, po = _out(n)
+    _check(lib().lcb_debug_tpke_miller(f, po, n, py, len(y_keys), pu, pw, pv, pvo, len(cts), pct, pdec, pui),
+           "debug_tpke_miller")
+    return [(list(f[144 * i:144 * i + 144]), bool(ob[i])) for i in range(n)]
 
 
 def batched_census():

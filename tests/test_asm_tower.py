@@ -131,8 +131,18 @@ def test_cyc_sqr_chain(lib, cyc_elems):
 
 
 def test_cyc_sqr_edge_values(lib):
-    """the identity and its conjugate-free edge: 1^2 = 1; p - 1 limbs exercise the 3p/8p ranges"""
+    """the identity and its conjugate-free edge: 1^2 = 1; p - 1 limbs exercise the 3p/8p ranges.  Off the cyclotomic
+    subgroup the routine computes the Granger-Scott polynomial map, not the square: the saturated operands and every
+    residue pattern of tests/tower_cases.py against the big-integer restatement of that map (tests/pyref/tower.py),
+    the same operands the device test feeds lcb_debug_asm_tower, so a disagreement between the two can be attributed"""
+    import tower_cases as C
+    from pyref import tower as T
     one = unflat([1] + [0] * 11)
     rinv = pow(R, -1, P)
     _, out = run_cyc_sqr(lib, one)
     assert [o * rinv % P for o in out] == flat(one)
+    for case in C.sat() + C.s_dense() + C.special():
+        lane, _ = asm_sim.call(lib, "lcb_r_cyc_sqr", {}, {12 * k: case.m[k] for k in range(12)})
+        out = [sum(lane.a[12 * k + j] << (32 * j) for j in range(12)) for k in range(12)]
+        assert all(o < P for o in out), case.name
+        assert out == T.gs_sqr_residues(case.m), case.name

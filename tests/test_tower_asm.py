@@ -173,6 +173,75 @@ def test_pow_z(prog, same):
     check_contract("lcb_r_pow_z", lane, {19, 20, 21, 22, 23, 60, 61, 30, 31})
 
 
+# ---------------------------------------------------------------- edge operands (tests/tower_cases.py), compared with the
+# big-integer model (tests/pyref/tower.py): the operands the device tests feed the same routines through
+# lcb_debug_asm_tower, so a later disagreement between simulator and GPU can be attributed to one of them
+import tower_cases as TC  # noqa: E402
+from pyref import bls12_381 as PB  # noqa: E402
+from pyref import tower as PT  # noqa: E402
+
+
+def test_fp2dw_residue_patterns(prog):
+    """every member of S (and its neighbours in S) as xa, xb, ya, yb: the carry chains of the double-width products"""
+    prg, labels = prog
+    v = [x for _, x in TC.S]
+    quads = [[v[(k + 5 * j) % len(v)] for j in range(4)] for k in range(len(v))]
+    quads += [[P - 1] * 4, [(1 << 380) - 1] * 4, [P - 1, 0, P - 1, 0], [0, P - 1, 0, P - 1], [P - 1, P - 1, 0, P - 1]]
+    for x in quads:
+        lane = new_lane()
+        for k, val in enumerate(x):
+            for j in range(12):
+                lane.v[12 * k + j] = (val >> (32 * j)) & 0xffffffff
+        lane.s[28] = lane.s[29] = 0
+        asm_sim.run_program(prg, labels, "lcb_r_fp2dw", lane)
+        rd = lambda base: sum(lane.v[base + j] << (32 * j) for j in range(24))      # noqa: E731
+        xa, xb, ya, yb = x
+        assert rd(72) == (xa * ya - xb * yb) % (1 << 768), x
+        assert rd(120) == (xa * yb + xb * ya), x
+
+
+def run_mul_n(prog, a, m, conj_a):
+    prg, labels = prog
+    lane = new_lane()
+    put_slot(lane, BASE_A, a)
+    put_slot(lane, BASE_M, m)
+    set_pair(lane, 56, BASE_A)
+    set_pair(lane, 20, BASE_M)
+    set_pair(lane, 22, BASE_D)
+    set_pair(lane, 60, BASE_D)
+    lane.s[65] = conj_a
+    asm_sim.run_program(prg, labels, "lcb_r_fp12_mul_n", lane)
+    return get_slot(lane, BASE_D)
+
+
+def test_fp12_mul_n_saturated(prog):
+    """the lazily reduced Fp6 products at their largest: saturated times saturated, and the residue patterns"""
+    sat, dense = TC.sat(), TC.s_dense()
+    pairs = [(sat[0], sat[0]), (sat[0], sat[2]), (sat[1], sat[5]), (sat[3], sat[4]), (sat[2], sat[2]), (sat[4], sat[0]),
+             (dense[0], dense[1]), (dense[2], sat[0]), (sat[0], dense[3]), (dense[3], dense[3])]
+    for k, (a, m) in enumerate(pairs):
+        conj_a = k & 1
+        got = run_mul_n(prog, a.m, m.m, conj_a)
+        fa = PT.residues_to_flat(a.m)
+        want = PB.e_mul(PB.e_conj(fa) if conj_a else fa, PT.residues_to_flat(m.m))
+        assert all(g < P for g in got), (a.name, m.name)
+        assert got == PT.flat_to_residues(want), (a.name, m.name, conj_a)
+
+
+@pytest.mark.parametrize("which", [1, 2 + len(TC.unit_sources())])
+def test_pow_z_unit_edges(prog, which):
+    """conj(B^|z|) on the easy-part image of the all-(p - 1) operand, and on a conjugate"""
+    prg, labels = prog
+    u = TC.unit()[which]
+    lane = new_lane()
+    put_slot(lane, BASE_M, u.m)
+    set_pair(lane, 20, BASE_M)
+    set_pair(lane, 22, BASE_T)
+    set_pair(lane, 60, BASE_D)
+    asm_sim.run_program(prg, labels, "lcb_r_pow_z", lane)
+    assert get_slot(lane, BASE_D) == PT.flat_to_residues(PT.pow_z(PT.residues_to_flat(u.m))), u.name
+
+
 # ---------------------------------------------------------------- the Miller loop routines (lcb_r_fp12sq, lcb_r_line,
 # lcb_r_miller2)
 sys.path.insert(0, os.path.join(ROOT, "tests", "pyref"))
