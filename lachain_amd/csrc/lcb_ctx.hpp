@@ -33,6 +33,72 @@ struct DevBuf {
     }
 };
 
+// The device buffers of the randomized batch check (lcb_batch.cpp), grown on demand (DevBuf::get) by the function named
+// last in each line.  n: the call's shares; a level's entries: its groups or singles.
+enum RlcBuf {
+    RLC_REC_A,        // per share, its exponent's multiple of U_i (TPKE) / of the key (CommonCoin): n Jacobian G1 records; rlc_ws
+    RLC_REC_B,        // per share, the multiple of Y_i (G1) / of the signature share (G2): n Jacobian records; rlc_ws
+    RLC_DESC_A,       // the current level's entry list, 16 B per entry, n entries; rlc_ws (swapped with DESC_B per level)
+    RLC_DESC_B,       // the next level's list (k_rlc_resolve / search append to it); the census's singles first; rlc_ws
+    RLC_CNT,          // the device counter block (RlcCnt words, 32 B); rlc_ws
+    RLC_GPTS,         // a level's summed points, one record per entry (RlcKindInfo::rec bytes); rlc_census / rlc_levels
+    RLC_GACC,         // a level's decisions, one byte per entry: Miller pre-flag, then the check's result; the same
+    RLC_GEX,          // per entry: its shares need exact single checks (W outside G2), set by the sums; the same
+    RLC_SDESC,        // level 2's descriptors of the failed level-1 groups, 16 B each (TPKE: twice as many, the open
+                      // groups' go behind them); rlc_levels at level 1
+    RLC_GAMMA,        // the level-1 groups' final-exponentiation values (gamma_0), 576 B per group; rlc_levels at level 1
+    RLC_WSUM,         // CommonCoin: the level-1 groups' weighted sums for level 2 (RlcKindInfo::wrec bytes); the same
+    RLC_KTAB,         // the keys' fixed-base tables and their workspace (lcbk_key_table_bytes); rlc_key_tables
+    RLC_SUSP,         // the suspect-key bitmap, one bit per key; rlc_ws when the call has a census
+    RLC_CVAL,         // per census share: its single was a valid check (feeds k_rlc_census_stats); rlc_census
+    RLC_MFB,          // the cooperative Miller kernel's fallback flags, one byte per check of a chunk; rlc_checks
+    RLC_G12,          // TPKE level 2: gamma_c rows, then gamma_t rows, 576 B per failed group each; rlc_levels
+    RLC_OPEN,         // TPKE level 2: the count (4 words) and list of groups the one-error search leaves open; rlc_levels
+    RLC_HOK,          // split preparation: H's hash validity per ciphertext, merged into t_ctok; the fused TPKE call
+    RLC_S2B_PARK,     // the two-error search's Fp12 slots (lcbk_tpke_rlc_search2b_asm_park_bytes); rlc_levels
+    RLC_PAIR_PARK,    // the level-1 pair stage's two park buffers (products + solos, then pass 2); rlc_fe_pairs
+    RLC_PAIR_LISTS,   // its job lists (FePairWs); rlc_fe_pairs
+    RLC_N
+};
+// The words of the device counter block RLC_CNT (the kernels take pointers to single words)
+enum RlcCnt {
+    CNT_GROUPS,       // the current level's entries (k_rlc_groups counts level 1's)
+    CNT_NEXT,         // the next level's entries (k_rlc_resolve and the searches)
+    CNT_SEARCH,       // failed level-1 groups handed to level 2 (k_rlc_resolve)
+    CNT_SUSPECTS,     // suspect keys (k_rlc_census_stats)
+    CNT_SPLIT,        // level-1 entries after the suspect split (k_rlc_suspect_split)
+    CNT_N
+};
+// Host-side names of the last batched call's statistics; the C ABI returns each array in this order
+enum RlcCensusStat {  // lcb_ctx::rlc_census
+    CENSUS_SHARES,    // shares the census checked one by one
+    CENSUS_SUSPECTS,  // keys it marked suspect
+    CENSUS_GROUPS,    // level-1 groups before the suspect split
+    CENSUS_ENTRIES,   // level-1 entries after it
+    CENSUS_N
+};
+enum FePairStat {     // lcb_ctx::fe_pair, the level-1 pair stage
+    FE_PAIRS_FORMED,
+    FE_PAIRS_FAILED,
+    FE_PASS1_JOBS,    // final exponentiations of pass 1
+    FE_PASS2_JOBS,    // and of pass 2
+    FE_PAIR_N
+};
+enum LvlKernelStat {  // lcb_ctx::lvl_kernel, the levels' final-exponentiation dispatches
+    LVL_ONE_LANE,     // on the one-lane kernel
+    LVL_NINE_LANE,    // on the nine-lane kernel
+    LVL_MOVED_BUSY,   // one-lane only because the call was overlapped
+    LVL_MAX_INFLIGHT, // the largest in-flight count seen
+    LVL_KERNEL_N
+};
+enum RlcMsStat {      // lcb_ctx::rlc_ms, accumulated over the levels
+    MS_SUMS,
+    MS_MILLER,
+    MS_FINAL_EXP,     // with the resolve / search behind it
+    MS_PREP,          // the fused call's preparation chain (0 for other calls)
+    RLC_MS_N
+};
+
 struct lcb_ctx {
     std::recursive_mutex mu;        // one enqueue at a time per context (contexts may be shared by threads)
     int device = 0;
@@ -43,7 +109,9 @@ struct lcb_ctx {
     size_t chunk = (size_t)1 << 21; // lcb_set_verify_chunk's value, read once per outermost enqueue (LCB_VERIFY_CHUNK)
     // TPKE workspace (lcb_*tpke_prepare_dev): line sets of H and W per ciphertext, validity, decompressed keys
     DevBuf t_lines, t_ctok, t_keys, t_f;
-    DevBuf t_coop[3];                 // small exact batches on the cooperative kernels: point records, checks, flags
+    DevBuf t_ctg2;                    // per ciphertext: W in G2, decided from its line set; written by every TPKE
+                                      // preparation (tpke_prepare, the fused batched call), read by the batch check's sums
+    DevBuf t_coop[3];                // small exact batches on the cooperative kernels: point records, checks, flags
     // prepared-ciphertext cache of lcb_tpke_verify_shares_cached (line sets + validity per slot, keyed by the bytes)
     DevBuf cc_lines, cc_ok;
     std::unordered_map<std::string, uint32_t> cc_map;
@@ -79,22 +147,17 @@ struct lcb_ctx {
     uint64_t pc_tick = 0;
     hipEvent_t ver_ev[3] = {};
     bool ver_ev_ready = false, ver_ran = false;
-    // randomized batch verification (k_batch.hip): r_i U_i / r_i Y_i records, group lists, group points, counts
-    DevBuf rlc[22];                   // [12]: the keys' fixed-base tables, [13] suspect-key bitmap, [14] census validity,
-                                      // [15] coop Miller fallback flags, [16] TPKE level-2 gamma_c / gamma_t rows, [17] its open groups,
-                                      // [18] H's hash validity (split preparation, fork mode 3), [20] the level-1 pair
-                                      // stage's two park buffers (products + solos, then pass 2), [21] its job lists
-    uint32_t fe_pair[4] = {};         // last call's pair stage: pairs formed, pairs failed, exponentiations of pass 1 / 2
-    uint32_t lvl_kernel[4] = {};      // last call's level final exponentiations: dispatches on the one-lane / nine-lane
-                                      // kernel, one-lane because the call was overlapped, largest in-flight count seen
+    // randomized batch verification (k_batch.hip, lcb_batch.cpp)
+    DevBuf rlc[RLC_N];
+    uint32_t fe_pair[FE_PAIR_N] = {};         // last call's pair stage
+    uint32_t lvl_kernel[LVL_KERNEL_N] = {};   // last call's level final exponentiations
     bool lvl_counted = false;         // this call holds a count in the device's in-flight counter (BatchedInflight)
     hipEvent_t rlc_ev[3] = {};
     hipEvent_t rlc_lev_ev[4] = {};    // per level: before sum / Miller / final exp / resolve
-    float rlc_ms[4] = {};             // accumulated over the levels of the last call: sums, Miller, final exp (+ resolve
-                                      // / search), the fused call's preparation chain (0 for other calls)
+    float rlc_ms[RLC_MS_N] = {};      // last call's phase times
     bool rlc_ev_ready = false, rlc_ran = false;
     uint32_t rlc_levels[8] = {};
-    uint32_t rlc_census[4] = {};      // census shares, suspect keys, level-1 groups before / entries after the split
+    uint32_t rlc_census[CENSUS_N] = {};
     int rlc_nlev = 0;
     uint64_t rlc_calls = 0;
     // which prepared line sets are not normalised (adversarial W): [0] the census's ciphertexts, [1] all; the one-lane

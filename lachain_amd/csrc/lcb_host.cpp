@@ -6,6 +6,8 @@
 // the calling thread, word for word the kernels' formulas, because a GPU round trip costs 50-100x the operation.
 // There is deliberately no CPU fallback for the GPU work: without a gfx950 device mclBn_init returns -1 and every
 // entry point fails (returns -1 / 0 bytes / leaves outputs zeroed) with lcb_last_error() describing why.
+// The randomized batch check (the *_batched entry points' driver) is lcb_batch.cpp; the exact checks and the
+// preparations both use are here.
 //
 // Concurrency model (the reference calls mcl from one thread per consensus protocol,
 // /root/reference/src/Lachain.Consensus/AbstractProtocol.cs:46-47):
@@ -40,7 +42,7 @@
 #include "fr_host.hpp"
 #include "fp_host.hpp"
 
-#define LCB_BLOCK 256
+using namespace lcb_int;
 
 namespace {
 
@@ -62,17 +64,6 @@ void set_err(const char *what, hipError_t e = hipSuccess) {
     g_err_count++;
 }
 
-// opt-in switches read from the environment at call time: the tuning hooks (lcb_set_coop_max, ...) change the kernel
-// families a batch runs on and the fault-injection hooks make calls fail; neither belongs in a production process
-bool env_on(const char *name) {
-    const char *e = getenv(name);
-    return e && e[0] == '1';
-}
-bool tuning_allowed(const char *what) {
-    if (env_on("LCB_ALLOW_TUNING")) return true;
-    set_err((std::string(what) + ": tuning hooks need LCB_ALLOW_TUNING=1").c_str());
-    return false;
-}
 // fault injection (lcb_test_inject_failure, LCB_ALLOW_TEST_HOOKS=1): the next `count` passes through site `site` fail
 std::atomic<int> g_inject_site{0}, g_inject_count{0};
 bool injected(int site) {
@@ -219,8 +210,6 @@ bool run_hash(size_t in_words, size_t out_words) {
 #define LOCKED_OR(ret)                        \
     if (!stage_ready()) return ret;
 
-inline u32 nblk(size_t n) { return (u32)((n + LCB_BLOCK - 1) / LCB_BLOCK); }
-
 // canonical Fr bytes (32-byte LE < r)
 bool fr_bytes_lt_r(const uint8_t *b) {
     for (int j = 7; j >= 0; j--) {
@@ -231,6 +220,18 @@ bool fr_bytes_lt_r(const uint8_t *b) {
 }
 
 } // namespace
+
+// opt-in switches read from the environment at call time: the tuning hooks (lcb_set_coop_max, ...) change the kernel
+// families a batch runs on and the fault-injection hooks make calls fail; neither belongs in a production process
+bool lcb_int::env_on(const char *name) {
+    const char *e = getenv(name);
+    return e && e[0] == '1';
+}
+bool lcb_int::tuning_allowed(const char *what) {
+    if (env_on("LCB_ALLOW_TUNING")) return true;
+    set_err((std::string(what) + ": tuning hooks need LCB_ALLOW_TUNING=1").c_str());
+    return false;
+}
 
 // ================================================================== init / config
 extern "C" int lcb_set_device(int id) {
@@ -247,6 +248,7 @@ extern "C" int lcb_set_line_mode(int general) {
     g_line_mode = general != 0;
     return 0;
 }
+int lcb_int::prepare_flags() { return g_orig_cofactor | (g_line_mode << 1); }
 extern "C" const char *lcb_last_error(void) { return g_err.c_str(); }
 
 // ================================================================== the scratch gate (gate.hpp LCB_LAUNCH_GATED)
@@ -944,7 +946,7 @@ extern "C" int mclBn_FrEvaluatePolynomial(mclBnFr *out, const mclBnFr *c, mclSiz
 // latency, but about half the work per set) for large batches
 #define LCB_LINES_COOP_MAX 8192
 std::atomic<int> g_lines_coop_max{LCB_LINES_COOP_MAX};
-void lines_fill(hipStream_t s, u32 *lines, size_t n, const u32 *sets, uint8_t *w_g2) {
+void lcb_int::lines_fill(hipStream_t s, u32 *lines, size_t n, const u32 *sets, uint8_t *w_g2) {
     if (!n) return;
     if (n <= (size_t)g_lines_coop_max.load()) lcbk_lineset_coop(s, lines, (u32)n, sets, w_g2);
     else lcbk_lineset_fill(dim3(nblk(n)), s, lines, (u32)n, sets, w_g2);
@@ -953,7 +955,7 @@ void lines_fill(hipStream_t s, u32 *lines, size_t n, const u32 *sets, uint8_t *w
 // `which` (0 = the census's ciphertexts, 1 = all) is reduced on the device and copied to pinned memory; the host reads
 // it (lines_unnormalised) before it enqueues the checks that use those sets and dispatches the one-lane Miller
 // fallback only when it is set.  Any failure reads as "set" (the fallback then runs, as before round 5).
-void lines_flag_enqueue(lcb_ctx *c, int which, const u32 *lines, u32 c0, u32 c1, hipStream_t s) {
+void lcb_int::lines_flag_enqueue(lcb_ctx *c, int which, const u32 *lines, u32 c0, u32 c1, hipStream_t s) {
     c->unn_set[which] = false;
     if (!c->unn_pin && hipHostMalloc((void **)&c->unn_pin, 16, hipHostMallocDefault) != hipSuccess) {
         c->unn_pin = nullptr;
@@ -969,9 +971,26 @@ void lines_flag_enqueue(lcb_ctx *c, int which, const u32 *lines, u32 c0, u32 c1,
     if (hipEventRecord(c->unn_ev[which], s) != hipSuccess) return;
     c->unn_set[which] = true;
 }
-bool lines_unnormalised(lcb_ctx *c, int which) {
+bool lcb_int::lines_unnormalised(lcb_ctx *c, int which) {
     if (!c->unn_set[which] || hipEventSynchronize(c->unn_ev[which]) != hipSuccess) return true;
     return __atomic_load_n(c->unn_pin + which, __ATOMIC_ACQUIRE) != 0;
+}
+// a *_prepared call runs on the exact shape (keys, ciphertexts / messages) its context's prepare recorded
+bool lcb_int::tpke_shape_ok(lcb_ctx *c, size_t n_keys, size_t n_cts, const char *what) {
+    if (!c->t_ready) { set_err((std::string(what) + ": no TPKE batch prepared in this context").c_str()); return false; }
+    if (c->t_n_cts != n_cts || c->t_n_keys != n_keys) {
+        set_err((std::string(what) + ": batch shape differs from the one prepared in this context").c_str());
+        return false;
+    }
+    return true;
+}
+bool lcb_int::ts_shape_ok(lcb_ctx *c, size_t n_pks, size_t n_msgs, const char *what) {
+    if (!c->s_ready) { set_err((std::string(what) + ": no threshold-signature batch prepared in this context").c_str()); return false; }
+    if (c->s_n_msgs != n_msgs || c->s_n_pks != n_pks) {
+        set_err((std::string(what) + ": batch shape differs from the one prepared in this context").c_str());
+        return false;
+    }
+    return true;
 }
 
 // ================================================================== execution contexts
@@ -981,7 +1000,7 @@ void ctx_free(lcb_ctx *c) {
     if (!c) return;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->order_valid) (void)hipEventSynchronize(c->order);
-    for (DevBuf *b : {&c->t_lines, &c->t_ctok, &c->t_keys, &c->t_f, &c->s_lines, &c->s_mok, &c->s_keys, &c->s_f})
+    for (DevBuf *b : {&c->t_lines, &c->t_ctok, &c->t_ctg2, &c->t_keys, &c->t_f, &c->s_lines, &c->s_mok, &c->s_keys, &c->s_f})
         b->release();
     for (auto &b : c->lag) b.release();
     c->lws.release();
@@ -1122,12 +1141,12 @@ int tpke_prepare(lcb_ctx *c, const uint8_t *d_y, size_t n_keys, const uint8_t *d
     u32 *lines = (u32 *)c->t_lines.get((size_t)n_cts * 2 * LCB_LINESET_BYTES);
     uint8_t *ctok = (uint8_t *)c->t_ctok.get(n_cts);
     void *keys = c->t_keys.get(n_keys * LCB_G1A_ST_BYTES);
-    uint8_t *ctg2 = (uint8_t *)c->rlc[8].get(n_cts);     // W in G2 (the batched check's flags), from the line sets
+    uint8_t *ctg2 = (uint8_t *)c->t_ctg2.get(n_cts);     // from the line sets, for the batch check's sums
     if (!lines || !ctok || !keys || !ctg2) { set_err("device allocation failed"); return -1; }
     if (n_keys) lcbk_g1_decompress(dim3(nblk(n_keys)), s, d_y, (u32)n_keys, keys);
     if (n_cts) {
-        lcbk_tpke_ct_prepare(dim3(nblk(n_cts)), s, d_u, d_w, d_v, d_voff, (u32)n_cts, lines, ctok,
-                             g_orig_cofactor | (g_line_mode << 1), nullptr);
+        lcbk_tpke_ct_prepare(dim3(nblk(n_cts)), s, d_u, d_w, d_v, d_voff, (u32)n_cts, lines, ctok, prepare_flags(),
+                             nullptr);
         lines_fill(s, lines, 2 * n_cts, nullptr, ctg2);
     }
     c->unn_census = 1;
@@ -1138,72 +1157,6 @@ int tpke_prepare(lcb_ctx *c, const uint8_t *d_y, size_t n_keys, const uint8_t *d
     c->t_gen++;
     c->t_ready = true;
     return 0;
-}
-bool tpke_shape_ok(lcb_ctx *c, size_t n_keys, size_t n_cts, const char *what) {
-    if (!c->t_ready) { set_err((std::string(what) + ": no TPKE batch prepared in this context").c_str()); return false; }
-    if (c->t_n_cts != n_cts || c->t_n_keys != n_keys) {
-        set_err((std::string(what) + ": batch shape differs from the one prepared in this context").c_str());
-        return false;
-    }
-    return true;
-}
-// level-2 two-error search on the assembly Fp12 products (k_tpke.hip k_tpke_rlc_search2b_asm, round 6)
-#ifndef LCB_SEARCH2B_ASM
-#define LCB_SEARCH2B_ASM 1
-#endif
-std::atomic<int> g_fork_mode{4};            // lcb_set_fork_mode: stream layout of the fused batched verify (1: measured
-                                            // 104.8 vs 117.8 ms per 1M-share TPKE step, profiles/r03/ab1; 3, the split
-                                            // preparation: 99.6 vs 103.2 ms, profiles/r03/ab8; 4, the split preparation
-                                            // in one dispatch on one high-priority stream: DESIGN.md §14.2)
-std::atomic<uint32_t> g_coop_max{32768};    // lcb_set_coop_max: batches / levels of <= this many checks use the 9-lane kernels
-std::atomic<uint32_t> g_coop_miller_max{65536};   // lcb_set_coop_miller_max: the same for the group Miller loops only
-                                                  // (65536: level 1 too, 105.5 vs 106.1 ms, profiles/r03/ab2)
-// The kernel form of a TPKE level's final exponentiation when batches overlap.  The nine-lane kernel
-// issues about 50 % more wave instructions per check than the one-lane kernel; they buy latency while a level is below
-// one wave per SIMD and nothing while other batches keep the SIMDs full.  g_batched_inflight counts, per device, the
-// batched TPKE verify calls between entry and return; a call that sees another one counted when it enqueues a level's
-// final exponentiation is overlapped, and then lcb_set_busy_coop_max's value decides instead of lcb_set_coop_max's.
-// Default 20,000: pass 1 of the headline batch's pair stage (23.8 K jobs) moves, pass 2 and level 2 (8.5 K and 9.4 K
-// checks, under one one-lane wave per SIMD) stay: moving them too measured no better than moving nothing (§18).
-#ifndef LCB_BUSY_COOP_MAX
-#define LCB_BUSY_COOP_MAX 20000u
-#endif
-static_assert(LCB_BUSY_COOP_MAX >= 1024u, "the aggregation queue's overlapping small flushes keep the nine-lane kernel");
-std::atomic<uint32_t> g_busy_coop_max{LCB_BUSY_COOP_MAX};   // UINT32_MAX: the rule is off
-std::atomic<int> g_level_mode{0};                 // lcb_set_level_mode: 0 by the count, 1 never overlapped, 2 always
-std::atomic<uint32_t> g_batched_inflight[64];
-struct BatchedInflight {                          // scope guard: every return of the counted call releases its count
-    lcb_ctx *c;
-    std::atomic<uint32_t> *a;
-    explicit BatchedInflight(lcb_ctx *c_)
-        : c(c_), a(c_->device >= 0 && c_->device < 64 && !c_->lvl_counted ? &g_batched_inflight[c_->device] : nullptr) {
-        if (a) { a->fetch_add(1); c->lvl_counted = true; }
-    }
-    ~BatchedInflight() {
-        if (a) { c->lvl_counted = false; a->fetch_sub(1); }
-    }
-    BatchedInflight(const BatchedInflight &) = delete;
-    BatchedInflight &operator=(const BatchedInflight &) = delete;
-};
-// the kernel of a final-exponentiation dispatch of m checks in the level driver: true = one-lane.  ruled: a TPKE level
-// (not CommonCoin, not a census chain), where the overlap rule may replace lcb_set_coop_max's
-bool fe_one_lane(lcb_ctx *c, size_t m, bool ruled) {
-    const bool lat_one = m > g_coop_max.load();
-    bool one = lat_one;
-    const uint32_t bm = g_busy_coop_max.load();
-    if (ruled) {
-        const int mode = g_level_mode.load();
-        uint32_t nfl = 0;
-        if (c->device >= 0 && c->device < 64) nfl = g_batched_inflight[c->device].load();
-        if (nfl > c->lvl_kernel[3]) c->lvl_kernel[3] = nfl;
-        const bool busy = mode == 2 || (mode == 0 && c->lvl_counted && nfl >= 2);
-        if (busy && bm != UINT32_MAX) {
-            one = m > bm;
-            if (one && !lat_one) c->lvl_kernel[2]++;
-        }
-    }
-    c->lvl_kernel[one ? 0 : 1]++;
-    return one;
 }
 // the exact check of n shares against prepared line sets (lines, ctok: n_cts ciphertexts) and decompressed keys
 int tpke_verify_core(lcb_ctx *c, const u32 *lines, const uint8_t *ctok, size_t n_cts, const void *keys, size_t n_keys,
@@ -1268,697 +1221,6 @@ int tpke_partial_decrypt_prepared(lcb_ctx *c, uint8_t *ui_out, uint8_t *status, 
     return launched("tpke partial decrypt launch") ? 0 : -1;
 }
 
-// Randomized batch verification (k_batch.hip header): the same accept / reject decisions as the exact per-share
-// checks, except with probability <= 2^-64 per group decision (the exponents are secret).  Groups are runs of shares
-// of one ciphertext (TPKE) / message (threshold signatures) in the caller's order: ciphertext- / message-major batches
-// give one group per ciphertext / message.  A level's group count comes back to the host (one 8-byte read per level).
-std::mutex g_seed_mu;                       // lcb_set_batch_seed (test hook) vs. the callers' key fills
-uint8_t g_rlc_seed[32];
-bool g_rlc_seed_set = false;
-std::atomic<size_t> g_census_min{16384};    // lcb_set_batch_census: batches of at least this many shares get a census
-enum RlcKind { RLC_TPKE = 0, RLC_TS = 1 };
-struct RlcStats {
-    bool valid = false;
-    int nlev = 0;
-    uint32_t levels[8] = {};
-    float ms[6] = {};
-    uint32_t census[4] = {};
-    uint32_t fe_pair[4] = {};
-};
-thread_local RlcStats t_rlc_stats;
-// cnt: [0] current level's groups, [1] next level's, [2] search entries, [3] suspect keys, [4] level-1 entries after
-// the suspect split; susp: the suspect-key bitmap; m: census shares [0, m)
-struct RlcWs {
-    u32 *rA, *rB;
-    uint8_t *dA, *dB;
-    u32 *cnt;
-    u32 *susp;
-    u32 m;
-    u32 *ktab = nullptr;               // the keys' fixed-base tables when built ahead of the fork (keys_first_tables)
-    uint8_t *kok = nullptr;
-    bool ktab_pre = false;
-};
-// the fused batched calls build the keys' fixed-base tables on the caller's stream BEFORE forking the preparation: a
-// key-table wave (277 registers) cannot be placed beside a preparation wave (346), so launched beside them the tables
-// (and the randomisation behind them) waited up to ~20 ms for the preparation to drain (profiles/r04/ab1)
-std::atomic<int> g_keys_first{1};
-u32 *rlc_key_tables(lcb_ctx *c, const void *keys, size_t n_keys, hipStream_t s, uint8_t **ktab_ok);
-void keys_first_tables(lcb_ctx *c, RlcWs &w, const void *keys, size_t n_keys, size_t n, hipStream_t s) {
-    if (!g_keys_first.load() || w.m >= n) return;
-    w.ktab = rlc_key_tables(c, keys, n_keys, s, &w.kok);
-    w.ktab_pre = true;
-}
-bool rlc_key_fill(lcb_ctx *c, u32 key[10]) {
-    bool fixed;
-    {
-        std::lock_guard<std::mutex> lk(g_seed_mu);
-        fixed = g_rlc_seed_set;
-        if (fixed) memcpy(key, g_rlc_seed, 32);
-    }
-    if (!fixed && getrandom(key, 32, 0) != 32) { set_err("batched verify: getrandom failed"); return false; }
-    c->rlc_calls++;
-    key[8] = (u32)c->rlc_calls;
-    key[9] = (u32)(c->rlc_calls >> 32);
-    return true;
-}
-// census size: a prefix of the batch large enough to sample every key a few times (>= 8 shares per key on average,
-// 512 .. 2048 shares), at most a quarter of the batch; 0 = no census (small batches, or disabled)
-u32 census_size(size_t n, size_t n_keys) {
-    const size_t min_n = g_census_min.load();
-    if (!min_n || n < min_n || n_keys < 2 || n_keys > 4096) return 0;
-    size_t m = std::min<size_t>(std::max<size_t>(512, 8 * n_keys), 2048);
-    m = std::min(m, n / 4);
-    return m < 16 ? 0 : (u32)m;
-}
-bool rlc_ws(lcb_ctx *c, RlcWs &w, size_t n, size_t rec_a, size_t rec_b, size_t n_keys, u32 m, hipStream_t s) {
-    w.rA = (u32 *)c->rlc[0].get(n * rec_a);
-    w.rB = (u32 *)c->rlc[1].get(n * rec_b);
-    w.dA = (uint8_t *)c->rlc[2].get(n * 16);
-    w.dB = (uint8_t *)c->rlc[3].get(n * 16);
-    w.cnt = (u32 *)c->rlc[4].get(32);
-    const size_t sw = (n_keys + 31) / 32;
-    w.susp = m ? (u32 *)c->rlc[13].get(4 * sw) : nullptr;
-    w.m = m;
-    if (!w.rA || !w.rB || !w.dA || !w.dB || !w.cnt || (m && !w.susp)) { set_err("device allocation failed"); return false; }
-    if (!c->rlc_ev_ready) {
-        for (auto &e : c->rlc_ev) hipEventCreate(&e);
-        for (auto &e : c->rlc_lev_ev) hipEventCreate(&e);
-        c->rlc_ev_ready = true;
-    }
-    // zeroed on the calling stream before any kernel of the call (the randomisation on the second stream reads
-    // the bitmap while the census writes it)
-    hipMemsetAsync(w.cnt, 0, 32, s);
-    if (m) hipMemsetAsync(w.susp, 0, 4 * sw, s);
-    c->rlc_census[0] = m;
-    c->prep_timed = false;
-    c->rlc_census[1] = c->rlc_census[2] = c->rlc_census[3] = 0;
-    return true;
-}
-// fixed-base tables of the batch's keys (k_rlc_key_tables), when the batch is large enough to repay them
-// (4 x 255 points per key, 64 lanes per key, ~24 additions of latency); nullptr: the points kernel multiplies the keys directly
-u32 *rlc_key_tables(lcb_ctx *c, const void *keys, size_t n_keys, hipStream_t s, uint8_t **ktab_ok) {
-    *ktab_ok = nullptr;
-    if (!n_keys || n_keys > 4096) return nullptr;
-    u32 *ws = (u32 *)c->rlc[12].get(lcbk_key_table_bytes((u32)n_keys));
-    if (!ws) return nullptr;
-    u32 *tab = nullptr;
-    lcbk_rlc_key_tables(dim3(1), s, keys, (u32)n_keys, ws, &tab, ktab_ok);
-    return tab;
-}
-// phase 1 (needs the decompressed keys only): per-share exponent multiples of shares [m, n) + level-1 groups (count
-// left on device in cnt[0])
-int rlc_points_enqueue(lcb_ctx *c, RlcWs &w, uint8_t *d_accept, size_t n, size_t n_keys, size_t n_cts,
-                       const uint32_t *d_ct, const uint32_t *d_dec, const uint8_t *d_ui, hipStream_t s) {
-    u32 key[10];
-    if (!rlc_key_fill(c, key)) return -1;
-    hipEventRecord(c->rlc_ev[0], s);
-    if (w.m < n) {
-        uint8_t *kok = w.kok;
-        u32 *ktab = w.ktab_pre ? w.ktab : rlc_key_tables(c, c->t_keys.p, n_keys, s, &kok);
-        lcbk_tpke_rlc_points(s, (u32)n_cts, c->t_keys.p, (u32)n_keys, d_ct, d_dec, d_ui, w.m, (u32)n, key, w.rA, w.rB,
-                             d_accept, ktab, kok, w.susp);
-        lcbk_rlc_groups(s, d_ct, w.m, (u32)n, (u32)n_cts, 32, w.dA, w.cnt);
-    }
-    hipEventRecord(c->rlc_ev[1], s);
-    return launched("tpke batched verify launch") ? 0 : -1;
-}
-int ts_rlc_points_enqueue(lcb_ctx *c, RlcWs &w, uint8_t *d_accept, size_t n, size_t n_pks, size_t n_msgs,
-                          const uint8_t *d_sigs, const uint32_t *d_midx, const uint32_t *d_pidx, hipStream_t s) {
-    u32 key[10];
-    if (!rlc_key_fill(c, key)) return -1;
-    hipEventRecord(c->rlc_ev[0], s);
-    if (w.m < n) {
-        uint8_t *kok = w.kok;
-        u32 *ktab = w.ktab_pre ? w.ktab : rlc_key_tables(c, c->s_keys.p, n_pks, s, &kok);
-        // decoded-share records for the assembly (optional: without the buffer the assembly decodes the shares)
-        const size_t rec = n * (size_t)LCB_TS_SHARE_REC_BYTES;
-        const bool grow = c->s_dec.cap < rec;
-        void *dec = c->s_dec.get(rec);
-        if (dec && grow) hipMemsetAsync(dec, 0, c->s_dec.cap, s);   // no record is valid until written
-        c->s_dec_n = dec ? c->s_dec.cap / LCB_TS_SHARE_REC_BYTES : 0;
-        lcbk_ts_rlc_points(s, (u32)n_msgs, c->s_keys.p, (u32)n_pks, d_midx, d_pidx, d_sigs, w.m, (u32)n, key, w.rA,
-                           w.rB, d_accept, w.dA, w.cnt, ktab, kok, w.susp, dec);
-        lcbk_rlc_groups(s, d_midx, w.m, (u32)n, (u32)n_msgs, 128, w.dA, w.cnt);
-    }
-    hipEventRecord(c->rlc_ev[1], s);
-    return launched("ts batched verify launch") ? 0 : -1;
-}
-bool read_counts(u32 *v, const u32 *d, int k, hipStream_t s) {
-    if (hipMemcpyAsync(v, d, 4 * k, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-        set_err("batched verify: group count");
-        return false;
-    }
-    return true;
-}
-struct RlcIo {                     // the per-share inputs the exact singles re-read
-    const uint32_t *d_key;         // dec_idx (TPKE) / pk_idx (TS)
-    const uint8_t *d_pts;          // ui (TPKE) / sigs (TS)
-    const uint32_t *d_grp;         // ct_idx (TPKE) / msg_idx (TS): the census singles' groups
-};
-struct RlcKindInfo {
-    bool ts;
-    bool fb = true;                   // TPKE: some line set the checks use may be un-normalised (dispatch the fallback)
-    const u32 *lines;
-    const uint8_t *okv, *ctg2;
-    const void *keys;
-    size_t n_keys, n_grp, rec, wrec;
-};
-RlcKindInfo rlc_kind(lcb_ctx *c, RlcKind kind) {
-    RlcKindInfo k;
-    k.ts = kind == RLC_TS;
-    k.lines = (const u32 *)(k.ts ? c->s_lines.p : c->t_lines.p);
-    k.okv = (const uint8_t *)(k.ts ? c->s_mok.p : c->t_ctok.p);
-    k.ctg2 = (const uint8_t *)c->rlc[8].p;
-    k.keys = k.ts ? c->s_keys.p : c->t_keys.p;
-    k.n_keys = k.ts ? c->s_n_pks : c->t_n_keys;
-    k.n_grp = k.ts ? c->s_n_msgs : c->t_n_cts;
-    k.rec = k.ts ? lcbk_ts_grp_bytes() : 2 * LCB_G1A_ST_BYTES;
-    k.wrec = k.ts ? LCB_G1_JAC_BYTES + LCB_G2_JAC_BYTES : 2 * LCB_G1_JAC_BYTES;
-    return k;
-}
-// the group sums / singles of a level's desc list -> gpts (k_*_rlc_sum)
-// the CommonCoin level sums on two lanes per group (1) or one (0: k_batch.hip); LCB_TS_SUM2 (with LCB_ALLOW_TUNING=1)
-// overrides it for A/B runs
-std::atomic<int> g_ts_sum2{[] {
-    const char *e = getenv("LCB_TS_SUM2");
-    return (e && env_on("LCB_ALLOW_TUNING")) ? atoi(e) : 1;
-}()};
-// (census: the CommonCoin census's 256-register copies, k_prep.hip)
-void rlc_sum_enqueue(const RlcKindInfo &K, RlcWs &w, const uint8_t *desc, u32 groups, bool first, uint8_t *d_accept,
-                     size_t n, RlcIo io, void *gpts, uint8_t *gex, u32 *wsum, uint8_t *cval, hipStream_t s,
-                     bool census = false) {
-    const u32 *susp = w.susp;
-    if (K.ts && census)
-        lcbk_ts_rlc_sum_census(dim3(nblk(groups)), s, desc, groups, first, K.okv, K.keys, (u32)K.n_keys, io.d_key,
-                               io.d_pts, w.rA, w.rB, (u32)n, gpts, d_accept, gex, wsum, susp, cval);
-    else if (K.ts && g_ts_sum2.load())          // two lanes per group (k_prep.hip)
-        lcbk_ts_rlc_sum2(s, desc, groups, first, K.okv, K.keys, (u32)K.n_keys, io.d_key, io.d_pts, w.rA, w.rB, (u32)n,
-                         gpts, d_accept, gex, wsum, susp, cval);
-    else if (K.ts)
-        lcbk_ts_rlc_sum(dim3(nblk(groups)), s, desc, groups, first, K.okv, K.keys, (u32)K.n_keys, io.d_key, io.d_pts,
-                        w.rA, w.rB, (u32)n, gpts, d_accept, gex, wsum, susp, cval);
-    else
-        // four lanes per group while the level is latency-bound, one when it is large (e.g. all singles)
-        lcbk_tpke_rlc_sum(dim3(nblk((groups <= 262144 ? 4 : 1) * (size_t)groups)), s, desc, groups,
-                          groups <= 262144 ? 4u : 1u, K.okv, K.ctg2, K.keys, (u32)K.n_keys, io.d_key,
-                          io.d_pts, w.rA, w.rB, (u32)n, gpts, d_accept, gex, wsum, susp, cval);
-}
-// Stage dump of the TPKE two-error search (test hook, LCB_ALLOW_TEST_HOOKS=1 and LCB_DUMP_SEARCH2B=<path prefix>):
-// before ("in") and after ("out") k_tpke_rlc_search2b, the open list, gamma_0 rows, gamma_c / gamma_t rows and the accept
-// bytes go to <prefix>.<stage>.<call>.bin — the header {ns, n_open, n, by_position} then the four arrays
-std::atomic<int> g_dump_calls{0};
-// Diagnostic builds (-DLCB_SEARCH2B_DEBUG=1) also record per (open check, lane) fingerprints inside the kernel: the
-// "in" stage returns the record buffer (set on the kernel), the "out" stage appends it to its file and frees it.
-void *search2b_dump(hipStream_t s, const char *stage, u32 ns, u32 no, const u32 *gamma, const u32 *g12, const u32 *open,
-                    const uint8_t *d_accept, size_t n, void *dbg = nullptr) {
-    const char *pre = getenv("LCB_DUMP_SEARCH2B");
-    if (!pre || !*pre || !env_on("LCB_ALLOW_TEST_HOOKS")) return nullptr;
-    if (hipStreamSynchronize(s) != hipSuccess) return nullptr;
-    std::vector<u32> rec;
-    if (stage[0] == 'o' && dbg) {
-        rec.resize((size_t)no * 32 * 8);
-        hipMemcpy(rec.data(), dbg, 4 * rec.size(), hipMemcpyDeviceToHost);
-        lcbk_search2b_debug(nullptr);
-        hipFree(dbg);
-    }
-    std::vector<u32> op(no + 4), g0((size_t)ns * 144), gg(2 * (size_t)ns * 144);
-    std::vector<uint8_t> acc(n);
-    hipMemcpy(op.data(), open, 4 * (no + 4), hipMemcpyDeviceToHost);
-    hipMemcpy(g0.data(), gamma, 4 * g0.size(), hipMemcpyDeviceToHost);
-    hipMemcpy(gg.data(), g12, 4 * gg.size(), hipMemcpyDeviceToHost);
-    hipMemcpy(acc.data(), d_accept, n, hipMemcpyDeviceToHost);
-    const int call = stage[0] == 'i' ? g_dump_calls.fetch_add(1) : g_dump_calls.load() - 1;
-    char path[512];
-    snprintf(path, sizeof path, "%s.%s.%d.bin", pre, stage, call);
-    FILE *fh = fopen(path, "wb");
-    if (!fh) return nullptr;
-    const u32 hdr[4] = {ns, no, (u32)n, (u32)lcbk_search2b_by_position()};
-    fwrite(hdr, 4, 4, fh);
-    fwrite(op.data(), 4, op.size(), fh);
-    fwrite(g0.data(), 4, g0.size(), fh);
-    fwrite(gg.data(), 4, gg.size(), fh);
-    fwrite(acc.data(), 1, acc.size(), fh);
-    if (!rec.empty()) fwrite(rec.data(), 4, rec.size(), fh);
-    fclose(fh);
-    void *buf = nullptr;
-    if (stage[0] == 'i' && hipMalloc(&buf, (size_t)no * 32 * 8 * 4) == hipSuccess) {
-        hipMemset(buf, 0xff, (size_t)no * 32 * 8 * 4);
-        if (lcbk_search2b_debug(buf) != 0) { hipFree(buf); buf = nullptr; }
-    }
-    return buf;
-}
-// The level-1 pair stage of the TPKE batch check (k_tpke.hip "level-1 pair stage"): one final exponentiation per pair
-// of randomized groups instead of one per group.  lcb_set_fe_pair_min: chunks of at least this many entries take it;
-// 0 = never, UINT32_MAX (the default) = more entries than lcb_set_coop_max's value, the chunks that would otherwise
-// take the one-lane final-exponentiation kernel (smaller, latency-bound levels keep their single pass).
-std::atomic<uint32_t> g_fe_pair_min{UINT32_MAX};
-bool fe_pair_wanted(size_t m) {
-    const uint32_t v = g_fe_pair_min.load(), cm = g_coop_max.load();
-    if (v == 0 || m < 2) return false;
-    if (v != UINT32_MAX) return m >= v;
-    return cm != UINT32_MAX && m > cm;
-}
-// the final exponentiations of a chunk's m entries (f: their Miller values, gacc: their pre-flags) in two passes: the
-// products of the pairs and the other entries, then, after one read of the count, the first member of every pair that
-// failed; leaves gacc and the failed entries' rows of f as the single pass does.  Each pass runs on the kernel its own
-// count selects (lcb_set_coop_max's rule, or lcb_set_busy_coop_max's when the call is overlapped: fe_one_lane).
-struct FePairWs {                  // the job lists in rlc[21]: one allocation, the u32 arrays first
-    u32 *cnt, *list, *p2idx;       // cnt[4] (k_fe_pair_list), pass 2's jobs, each job's place among them
-    uint8_t *kind, *pacc, *pacc2;  // per job: its kind and pass 1's flag; per pass-2 entry: its flag
-    static size_t bytes(u32 jobs) { return 16 + (size_t)jobs * (4 + 4 + 1 + 1 + 1); }
-    explicit FePairWs(void *p, u32 jobs)
-        : cnt((u32 *)p), list(cnt + 4), p2idx(list + jobs), kind((uint8_t *)(p2idx + jobs)), pacc(kind + jobs),
-          pacc2(pacc + jobs) {}
-};
-bool rlc_fe_pairs(lcb_ctx *c, const uint8_t *desc, u32 *f, u32 m, uint8_t *gacc, hipStream_t s) {
-    const u32 jobs = (m + 1) / 2;
-    const size_t park_words = (size_t)jobs * 144 * (size_t)lcbk_fe_slots();
-    // pass 1's slots, then pass 2's: sized for the worst case (every job listed) so that no allocation follows the
-    // count's read
-    u32 *park = (u32 *)c->rlc[20].get(2 * park_words * 4);
-    void *lists = c->rlc[21].get(FePairWs::bytes(jobs));
-    if (!park || !lists) { set_err("device allocation failed (pair stage)"); return false; }
-    u32 *park2 = park + park_words;
-    const FePairWs ws(lists, jobs);
-    u32 *cnt = ws.cnt, *list = ws.list, *p2idx = ws.p2idx;
-    uint8_t *kind = ws.kind, *pacc = ws.pacc, *pacc2 = ws.pacc2;
-    hipMemsetAsync(cnt, 0, 16, s);
-    lcbk_fe_pair_pack(s, desc, f, m, park, jobs, kind, pacc);
-    if (!fe_one_lane(c, jobs, true)) lcbk_coop_final_exp_check_2w(s, park, jobs, pacc);
-    else lcbk_final_exp_check(dim3(nblk(jobs)), s, park, jobs, pacc);
-    lcbk_fe_pair_list(s, kind, pacc, jobs, list, p2idx, cnt);
-    u32 h[3] = {0, 0, 0};
-    if (!launched("batched verify launch") || !read_counts(h, cnt, 3, s)) return false;
-    const u32 n2 = h[0];
-    if (n2 > jobs) { set_err("batched verify: pair stage count"); return false; }
-    if (n2) {
-        lcbk_fe_pair_gather(s, f, m, list, n2, park2, pacc2);
-        if (!fe_one_lane(c, n2, true)) lcbk_coop_final_exp_check_2w(s, park2, n2, pacc2);
-        else lcbk_final_exp_check(dim3(nblk(n2)), s, park2, n2, pacc2);
-    }
-    lcbk_fe_pair_finish(s, f, m, park, jobs, kind, pacc, p2idx, park2, n2, gacc);
-    c->fe_pair[0] += h[1];
-    c->fe_pair[1] += h[2];
-    c->fe_pair[2] += jobs;
-    c->fe_pair[3] += n2;
-    return true;
-}
-// Miller + final exponentiation (+ resolve / search) over the groups of desc in chunks; gpts holds the points
-enum RlcStage { RLC_RESOLVE = 0, RLC_SEARCH = 1, RLC_COPY = 2 };   // after a chunk's checks: resolve / search / copy out
-bool rlc_checks(lcb_ctx *c, const RlcKindInfo &K, RlcWs &w, const uint8_t *desc, u32 count, void *gpts, uint8_t *gacc,
-                u32 *f, RlcStage stage, bool first, uint8_t *gex, uint4 *sdesc, u32 *gamma, uint8_t *d_accept,
-                RlcIo io, hipStream_t s, const u32 *copy_map = nullptr, bool census = false) {
-    hipEvent_t *ev = c->rlc_lev_ev;
-    const bool tsc = census && K.ts;      // the CommonCoin census: the 256-register copies (k_prep.hip)
-    float t;
-    for (size_t o = 0; o < count; o += LCB_VERIFY_CHUNK) {
-        const size_t m = count - o < LCB_VERIFY_CHUNK ? count - o : LCB_VERIFY_CHUNK;
-        hipEventRecord(ev[1], s);
-        // small levels (below one wave per SIMD as one check per lane): nine lanes per check (k_coop.hip)
-        // (the final exponentiation's form also depends on the batches in flight: fe_one_lane)
-        const bool coop_ml = m <= g_coop_miller_max.load();
-        const bool pairs = stage == RLC_RESOLVE && first && !K.ts && !census && fe_pair_wanted(m);
-        if (tsc)
-            lcbk_ts_rlc_miller_census(dim3(nblk(m)), s, K.lines, desc + 16 * o, (const uint8_t *)gpts + K.rec * o,
-                                      (u32)m, f, gacc + o);
-        else if (K.ts)
-            lcbk_ts_rlc_miller(dim3(nblk(m)), s, K.lines, desc + 16 * o, (const uint8_t *)gpts + K.rec * o, (u32)m, f,
-                               gacc + o);
-        else if (coop_ml)
-            lcbk_coop_tpke_miller(s, K.lines, desc + 16 * o, (const uint8_t *)gpts + K.rec * o, (u32)m, f, gacc + o,
-                                  (uint8_t *)c->rlc[15].get(m), 2, K.fb ? 1 : 0);
-        else
-            lcbk_tpke_rlc_miller(dim3(nblk(m)), s, K.lines, desc + 16 * o, (const uint8_t *)gpts + K.rec * o, (u32)m, f,
-                                 gacc + o);
-        hipEventRecord(ev[2], s);
-        // the nine-lane final exponentiation at 248 registers (k_prep.hip): it shares a SIMD with a randomisation wave
-        // of the batches in flight (three TPKE batches: 15.50-15.78 vs 15.26-15.46 M/s, profiles/r05/abfe2w)
-        if (pairs) {                      // (the time of both passes, with the count's read between them)
-            if (!rlc_fe_pairs(c, desc + 16 * o, f, (u32)m, gacc + o, s)) return false;
-        } else if (!fe_one_lane(c, m, !K.ts && !census)) lcbk_coop_final_exp_check_2w(s, f, (u32)m, gacc + o);
-        else lcbk_final_exp_check(dim3(nblk(m)), s, f, (u32)m, gacc + o);
-        hipEventRecord(ev[3], s);
-        if (stage == RLC_COPY)
-            lcbk_rlc_park_copy(s, f, (u32)o, (u32)m, gamma, copy_map);
-        else if (stage == RLC_SEARCH)
-            lcbk_rlc_search(dim3(nblk(m)), s, sdesc, (u32)o, (u32)m, gamma, f, d_accept, w.dB, w.cnt + 1, io.d_key,
-                            (u32)K.n_keys, w.susp);
-        else
-            lcbk_rlc_resolve(dim3(nblk(m)), s, desc, (u32)o, (u32)m, gacc, gex, f, first ? 1u : 0u, d_accept, w.dB,
-                             w.cnt + 1, sdesc, w.cnt + 2, gamma, io.d_key, (u32)K.n_keys, w.susp);
-        if (hipEventSynchronize(ev[3]) == hipSuccess) {
-            if (hipEventElapsedTime(&t, ev[1], ev[2]) == hipSuccess) c->rlc_ms[1] += t;
-            if (hipEventElapsedTime(&t, ev[2], ev[3]) == hipSuccess) c->rlc_ms[2] += t;
-        }
-    }
-    return true;
-}
-// the census (SURVEY-style Byzantine validators, k_batch.hip "suspect keys"): exact single checks of shares [0, m),
-// then the suspect-key bitmap and its count (cnt[3]); everything stays on the device (no host read)
-int rlc_census(lcb_ctx *c, RlcKind kind, RlcWs &w, uint8_t *d_accept, RlcIo io, hipStream_t s) {
-    if (!w.m) return 0;
-    RlcKindInfo K = rlc_kind(c, kind);
-    if (!K.ts) K.fb = lines_unnormalised(c, c->unn_census);    // waits for the census ciphertexts' line sets
-    const u32 m = w.m;
-    // the census uses dB as its desc list (dA is the level-1 list being built on the second stream)
-    void *gpts = c->rlc[5].get((size_t)m * K.rec);
-    uint8_t *gacc = (uint8_t *)c->rlc[6].get(m), *gex = (uint8_t *)c->rlc[7].get(m);
-    uint8_t *cval = (uint8_t *)c->rlc[14].get(m);
-    u32 *f = (u32 *)c->t_f.get((size_t)m * 576 * (size_t)lcbk_fe_slots());
-    if (!gpts || !gacc || !gex || !cval || !f) { set_err("device allocation failed"); return -1; }
-    lcbk_rlc_census_desc(s, io.d_grp, io.d_key, m, (u32)K.n_grp, (u32)K.n_keys, w.dB, d_accept);
-    RlcWs cw = w;
-    cw.susp = nullptr;                  // the census singles are exact checks whatever the bitmap says
-    rlc_sum_enqueue(K, cw, w.dB, m, false, d_accept, m, io, gpts, gex, nullptr, cval, s, true);
-    rlc_checks(c, K, cw, w.dB, m, gpts, gacc, f, RLC_RESOLVE, false, gex, nullptr, nullptr, d_accept, io, s, nullptr,
-               true);
-    lcbk_rlc_census_stats(s, io.d_key, m, (u32)K.n_keys, cval, d_accept, w.susp, w.cnt + 3);
-    return launched("batched verify census launch") ? 0 : -1;
-}
-// phase 2 (after the preparation and the randomisation): level 1 group checks (with suspect keys: the groups summed
-// over the other keys, every share of a suspect key as an exact single); level 2: weighted re-check + search of the
-// failed groups; then single checks
-int rlc_levels(lcb_ctx *c, RlcKind kind, RlcWs &w, uint8_t *d_accept, size_t n, RlcIo io, hipStream_t s) {
-    RlcKindInfo K = rlc_kind(c, kind);
-    u32 cnt[5] = {0, 0, 0, 0, 0};
-    for (auto &m : c->rlc_ms) m = 0.0f;
-    for (auto &v : c->fe_pair) v = 0;
-    for (auto &v : c->lvl_kernel) v = 0;
-    if (!read_counts(cnt, w.cnt, 4, s)) return -1;
-    if (!K.ts) K.fb = lines_unnormalised(c, 1) || (c->unn_census == 0 && lines_unnormalised(c, 0));
-    u32 groups = cnt[0];
-    c->rlc_census[1] = cnt[3];
-    c->rlc_census[2] = c->rlc_census[3] = groups;
-    hipEvent_t *ev = c->rlc_lev_ev;
-    float t;
-    if (cnt[3] && groups) {             // suspect keys: split their shares out of the level-1 groups
-        lcbk_rlc_suspect_split(s, w.dA, groups, io.d_key, (u32)K.n_keys, w.susp, d_accept, w.dB, w.cnt + 4);
-        if (!launched("batched verify launch") || !read_counts(cnt + 4, w.cnt + 4, 1, s)) return -1;
-        groups = cnt[4];
-        c->rlc_census[3] = groups;
-        std::swap(w.dA, w.dB);
-    } else {
-        w.susp = nullptr;               // no suspect key: the sums need not test the bitmap
-    }
-    for (int lev = 0; groups; lev++) {
-        if (lev > 40) { set_err("batched verify: group splitting did not terminate"); return -1; }
-        if (lev < 8) c->rlc_levels[lev] = groups;
-        c->rlc_nlev = lev + 1;
-        const bool first = lev == 0;
-        void *gpts = c->rlc[5].get((size_t)groups * K.rec);
-        uint8_t *gacc = (uint8_t *)c->rlc[6].get(groups), *gex = (uint8_t *)c->rlc[7].get(groups);
-        const size_t nf = groups < LCB_VERIFY_CHUNK ? groups : LCB_VERIFY_CHUNK;
-        u32 *f = (u32 *)c->t_f.get(nf * 576 * (size_t)lcbk_fe_slots());
-        uint4 *sdesc = nullptr;
-        u32 *gamma = nullptr, *wsum = nullptr;
-        if (first) {
-            sdesc = (uint4 *)c->rlc[9].get((size_t)groups * 16 * (K.ts ? 1 : 2));
-            gamma = (u32 *)c->rlc[10].get((size_t)groups * 576);
-            if (K.ts) wsum = (u32 *)c->rlc[11].get((size_t)groups * K.wrec);   // (TPKE: formed at level 2)
-        }
-        if (!gpts || !gacc || !gex || !f || (first && (!sdesc || !gamma || (K.ts && !wsum)))) {
-            set_err("device allocation failed");
-            return -1;
-        }
-        hipMemsetAsync(w.cnt + 1, 0, 8, s);
-        hipEventRecord(ev[0], s);
-        rlc_sum_enqueue(K, w, w.dA, groups, first, d_accept, n, io, gpts, gex, wsum, nullptr, s);
-        hipEventRecord(ev[1], s);
-        if (hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess)
-            c->rlc_ms[0] += t;
-        if (!rlc_checks(c, K, w, w.dA, groups, gpts, gacc, f, RLC_RESOLVE, first, gex, sdesc, gamma, d_accept, io, s))
-            return -1;
-        if (!launched("batched verify launch")) return -1;
-        if (!read_counts(cnt, w.cnt, 3, s)) return -1;
-        if (first && cnt[2] && !K.ts) {  // TPKE level 2: weighted re-check per failed group, one-error search, then
-            // for the groups it leaves open a second weighted check and the two-error location
-            const u32 ns = cnt[2];
-            if (lev + 1 < 8) c->rlc_levels[lev + 1] = ns;
-            c->rlc_nlev = ++lev + 1;
-            const size_t nf2 = ns < LCB_VERIFY_CHUNK ? ns : LCB_VERIFY_CHUNK;
-            void *gp2 = c->rlc[5].get((size_t)ns * K.rec);
-            uint8_t *gacc2 = (uint8_t *)c->rlc[6].get(ns);
-            u32 *g12 = (u32 *)c->rlc[16].get(2 * (size_t)ns * 576);     // gamma_c rows, then gamma_t rows
-            u32 *f2 = (u32 *)c->t_f.get(nf2 * 576 * (size_t)lcbk_fe_slots());
-            u32 *open = (u32 *)c->rlc[17].get((size_t)ns * 4 + 16);    // unresolved groups + their count
-            if (!gp2 || !gacc2 || !g12 || !f2 || !open) { set_err("device allocation failed"); return -1; }
-            hipEventRecord(ev[0], s);
-            lcbk_tpke_rlc_wsum2(s, sdesc, ns, nullptr, w.rA, w.rB, (u32)n, io.d_key, (u32)K.n_keys, w.susp, gp2, nullptr);
-            hipEventRecord(ev[1], s);
-            if (hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess)
-                c->rlc_ms[0] += t;
-            rlc_checks(c, K, w, (const uint8_t *)sdesc, ns, gp2, gacc2, f2, RLC_COPY, false, nullptr, sdesc, g12,
-                       d_accept, io, s);
-            lcbk_tpke_rlc_search2a(s, sdesc, ns, gamma, g12, d_accept, open + 4, open);
-            u32 no = 0;
-            if (!launched("batched verify launch") || !read_counts(&no, open, 1, s)) return -1;
-            if (no) {
-                if (lev + 1 < 8) c->rlc_levels[lev + 1] = no;
-                c->rlc_nlev = ++lev + 1;
-                hipEventRecord(ev[0], s);
-                // sdesc[ns, 2 ns) is free (sized for two entries per level-1 group): the open groups' descriptors
-                lcbk_tpke_rlc_wsum2(s, sdesc, no, open + 4, w.rA, w.rB, (u32)n, io.d_key, (u32)K.n_keys, w.susp, gp2,
-                                    sdesc + ns);
-                hipEventRecord(ev[1], s);
-                if (hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess)
-                    c->rlc_ms[0] += t;
-                // gamma_t of open group g -> row ns + g
-                rlc_checks(c, K, w, (const uint8_t *)(sdesc + ns), no, gp2, gacc2, f2, RLC_COPY, false, nullptr,
-                           sdesc + ns, g12 + (size_t)ns * 144, d_accept, io, s,
-                           lcbk_search2b_by_position() ? nullptr : open + 4);
-                void *dbg = search2b_dump(s, "in", ns, no, gamma, g12, open, d_accept, n);
-#if LCB_SEARCH2B_ASM
-                u32 *s2b_park = (u32 *)c->rlc[19].get(lcbk_tpke_rlc_search2b_asm_park_bytes(no));
-                if (!s2b_park) { set_err("device allocation failed (level-2 search slots)"); return -1; }
-                lcbk_tpke_rlc_search2b_asm(s, sdesc, ns, no, gamma, g12, open + 4, open, d_accept, w.dB, w.cnt + 1,
-                                           io.d_key, (u32)K.n_keys, w.susp, s2b_park);
-#else
-                lcbk_tpke_rlc_search2b(s, sdesc, ns, no, gamma, g12, open + 4, open, d_accept, w.dB, w.cnt + 1,
-                                       io.d_key, (u32)K.n_keys, w.susp);
-#endif
-                search2b_dump(s, "out", ns, no, gamma, g12, open, d_accept, n, dbg);
-            }
-            if (!launched("batched verify launch")) return -1;
-            if (!read_counts(cnt + 1, w.cnt + 1, 1, s)) return -1;
-        } else if (first && cnt[2]) {    // level 2: weighted re-check of the failed groups, then the search
-            const u32 ns = cnt[2];
-            if (lev + 1 < 8) c->rlc_levels[lev + 1] = ns;
-            c->rlc_nlev = ++lev + 1;
-            void *gp2 = c->rlc[5].get((size_t)ns * K.rec);   // (ns <= groups: the level-1 buffers are large enough)
-            hipEventRecord(ev[0], s);
-            if (K.ts) lcbk_ts_rlc_wsum(dim3(nblk(ns)), s, sdesc, ns, wsum, groups, gp2);
-            else lcbk_tpke_rlc_wsum(dim3(nblk(ns)), s, sdesc, ns, wsum, groups, gp2);
-            hipEventRecord(ev[1], s);
-            if (hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess)
-                c->rlc_ms[0] += t;
-            rlc_checks(c, K, w, (const uint8_t *)sdesc, ns, gp2, gacc, f, RLC_SEARCH, false, nullptr, sdesc, gamma,
-                       d_accept, io, s);
-            if (!launched("batched verify launch")) return -1;
-            if (!read_counts(cnt + 1, w.cnt + 1, 1, s)) return -1;
-        }
-        groups = cnt[1];
-        std::swap(w.dA, w.dB);            // the next level's groups
-    }
-    hipEventRecord(c->rlc_ev[2], s);
-    c->rlc_ran = true;
-    // the calling thread's copy of the statistics (lcb_tpke_batched_stats without a context)
-    RlcStats &st = t_rlc_stats;
-    st.valid = hipEventSynchronize(c->rlc_ev[2]) == hipSuccess;
-    if (st.valid && c->prep_timed && hipEventElapsedTime(&c->rlc_ms[3], c->prep_ev[0], c->prep_ev[1]) != hipSuccess)
-        c->rlc_ms[3] = -1.0f;
-    if (st.valid && c->prep_timed && getenv("LCB_PREP_TRACE")) {       // diagnostics: hashing / line sets + census
-        float a = -1.0f, b = -1.0f;
-        hipEventElapsedTime(&a, c->prep_ev[0], c->prep_ev[2]);
-        hipEventElapsedTime(&b, c->prep_ev[2], c->prep_ev[1]);
-        fprintf(stderr, "prep_trace hash %.2f lines+census %.2f ms\n", a, b);
-    }
-    st.nlev = c->rlc_nlev;
-    for (int i = 0; i < 8; i++) st.levels[i] = i < c->rlc_nlev ? c->rlc_levels[i] : 0;
-    for (int i = 0; i < 2; i++)
-        if (!st.valid || hipEventElapsedTime(&st.ms[i], c->rlc_ev[i], c->rlc_ev[i + 1]) != hipSuccess) st.ms[i] = -1.0f;
-    for (int i = 0; i < 4; i++) st.ms[2 + i] = c->rlc_ms[i];
-    for (int i = 0; i < 4; i++) st.census[i] = c->rlc_census[i];
-    for (int i = 0; i < 4; i++) st.fe_pair[i] = c->fe_pair[i];
-    return launched("batched verify launch") ? 0 : -1;
-}
-int tpke_verify_prepared_rlc(lcb_ctx *c, uint8_t *d_accept, size_t n, size_t n_keys, size_t n_cts, const uint32_t *d_ct,
-                             const uint32_t *d_dec, const uint8_t *d_ui, hipStream_t s) {
-    if (!tpke_shape_ok(c, n_keys, n_cts, "tpke batched verify")) return -1;
-    if (n > 0xffffffffu) { set_err("tpke batched verify: batch too large"); return -1; }
-    c->rlc_nlev = 0;
-    if (!n) return 0;
-    RlcWs w;
-    const RlcIo io{d_dec, d_ui, d_ct};
-    if (!rlc_ws(c, w, n, LCB_G1_JAC_BYTES, LCB_G1_JAC_BYTES, n_keys, census_size(n, n_keys), s)) return -1;
-    if (rlc_census(c, RLC_TPKE, w, d_accept, io, s)) return -1;   // before the randomisation: suspects skip it
-    if (rlc_points_enqueue(c, w, d_accept, n, n_keys, n_cts, d_ct, d_dec, d_ui, s)) return -1;
-    return rlc_levels(c, RLC_TPKE, w, d_accept, n, io, s);
-}
-bool fork_ready(lcb_ctx *c) {
-    if (c->fork_ready) return true;
-    int least = 0, greatest = 0;
-    hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-    if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->hi, hipStreamNonBlocking, greatest);
-    for (auto &ev : c->fork_ev)
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    for (auto &ev : c->prep_ev)
-        if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e != hipSuccess) { set_err("batched verify: stream creation", e); return false; }
-    c->fork_ready = true;
-    return true;
-}
-// fork mode 0's second normal-priority stream, created on first use
-bool aux_ready(lcb_ctx *c) {
-    if (c->aux) return true;
-    hipError_t e = hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking);
-    if (e != hipSuccess) { c->aux = nullptr; set_err("batched verify: stream creation", e); return false; }
-    return true;
-}
-// fork mode 3's two more preparation streams, created on first use: HIP hands every stream a hardware queue when it
-// is created (GPU_MAX_HW_QUEUES per priority, shared round-robin beyond that), so streams a context never uses would
-// still crowd the other contexts' queues
-bool split_ready(lcb_ctx *c) {
-    if (c->hi2) return true;
-    int least = 0, greatest = 0;
-    hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-    if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->hi2, hipStreamNonBlocking, greatest);
-    if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->hi3, hipStreamNonBlocking, greatest);
-    if (e != hipSuccess) { set_err("batched verify: stream creation", e); return false; }
-    return true;
-}
-// prepare + batched verify in one call: the randomisation (needs only the keys) runs on the context's second
-// stream beside the per-ciphertext hashing / line sets and the census (latency-bound: < 1 wave per SIMD for 50 K
-// ciphertexts); a key the census marks suspect before the randomisation reaches its shares skips them
-int tpke_verify_shares_rlc_fused(lcb_ctx *c, uint8_t *d_accept, size_t n, const uint8_t *d_y, size_t n_keys,
-                                 const uint8_t *d_u, const uint8_t *d_w, const uint8_t *d_v, const uint32_t *d_voff,
-                                 size_t n_cts, const uint32_t *d_ct, const uint32_t *d_dec, const uint8_t *d_ui,
-                                 hipStream_t s) {
-    const BatchedInflight counted(c);          // until this call returns: the level driver's overlap rule (fe_one_lane)
-    if (n_cts > 0xffffffffu || n_keys > 0xffffffffu || n > 0xffffffffu) { set_err("tpke batched verify: batch too large"); return -1; }
-    c->t_ready = false;
-    c->unn_set[0] = c->unn_set[1] = false;     // the fallback flags describe the line sets prepared below
-    c->rlc_nlev = 0;
-    u32 *lines = (u32 *)c->t_lines.get((size_t)n_cts * 2 * LCB_LINESET_BYTES);
-    uint8_t *ctok = (uint8_t *)c->t_ctok.get(n_cts);
-    void *keys = c->t_keys.get(n_keys * LCB_G1A_ST_BYTES);
-    uint8_t *ctg2 = (uint8_t *)c->rlc[8].get(n_cts);     // W in G2, from the line sets (k_lineset_fill)
-    if (!lines || !ctok || !keys || !ctg2) { set_err("device allocation failed"); return -1; }
-    if (!fork_ready(c)) return -1;
-    const int fm = g_fork_mode.load();
-    const bool hp = fm >= 1, prep_first = fm >= 2 && n_cts, split = fm >= 3, one_hi = fm == 4;
-    // split mode with a census: the ciphertexts of the census shares [0, m) (indices read to the host before this call
-    // launches anything; used when they all lie below a small bound c_early) are prepared first, on the preparation
-    // stream, so the census runs while the bulk is prepared
-    u32 c_early = 0;
-    const u32 m_census = n ? census_size(n, n_keys) : 0;
-    if (n_cts && split && !one_hi && m_census) {
-        std::vector<uint32_t> ci(m_census);
-        if (hipMemcpyAsync(ci.data(), d_ct, 4 * (size_t)m_census, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) { set_err("tpke batched verify: census index read"); return -1; }
-        u32 mx = 0;
-        for (uint32_t x : ci) mx = std::max(mx, x);
-        if ((size_t)mx + 1 < n_cts && mx < 4096u) c_early = mx + 1;
-    }
-    const int fl = g_orig_cofactor | (g_line_mode << 1);
-    // the census ciphertexts' decode + hash needs no key: it starts before the keys' decompression and tables (≈ 2 ms
-    // on an otherwise idle device in a single batch), ordered after the context's earlier work like the caller's stream
-    // (c_early is set in split mode only, whose preparation stream is c->hi)
-    const bool early = c_early != 0;
-    if (early) {
-        hipEventRecord(c->fork_ev[4], s);
-        hipStreamWaitEvent(c->hi, c->fork_ev[4], 0);
-        hipEventRecord(c->prep_ev[0], c->hi);
-        lcbk_tpke_ct_prepare_w64(c->hi, d_u, d_w, d_v, d_voff, c_early, lines, ctok, fl);
-    }
-    if (n_keys) lcbk_g1_decompress(dim3(nblk(n_keys)), s, d_y, (u32)n_keys, keys);
-    RlcWs w;
-    const RlcIo io{d_dec, d_ui, d_ct};
-    // mode 0: randomisation on the second stream, preparation + census on the caller's; mode 1: the latency-bound
-    // preparation chain (one lane per ciphertext / line set, < 1.5 waves per SIMD) on a high-priority stream, so
-    // its waves are dispatched ahead of the randomisation's 16 K waves, which run on the caller's stream
-    if (!hp && !aux_ready(c)) return -1;
-    hipStream_t sr = hp ? s : c->aux, sp = hp ? c->hi : s;
-    if (n) {
-        if (!rlc_ws(c, w, n, LCB_G1_JAC_BYTES, LCB_G1_JAC_BYTES, n_keys, m_census, s)) return -1;
-        keys_first_tables(c, w, keys, n_keys, n, s);
-        hipEventRecord(c->fork_ev[0], s);
-        hipStreamWaitEvent(hp ? sp : sr, c->fork_ev[0], 0);
-        if (hp && !early) hipEventRecord(c->prep_ev[0], sp);
-        if (!prep_first && rlc_points_enqueue(c, w, d_accept, n, n_keys, n_cts, d_ct, d_dec, d_ui, sr)) return -1;
-        if (!hp) hipEventRecord(c->fork_ev[1], sr);
-    } else if (hp) {
-        hipEventRecord(c->fork_ev[0], s);
-        hipStreamWaitEvent(sp, c->fork_ev[0], 0);
-        hipEventRecord(c->prep_ev[0], sp);
-    }
-    if (n_cts && split) {
-        // split preparation: hash + H's line set per lane, U / W decompression + W's line set (and its G2 flag) per
-        // lane, on separate high-priority streams; each lane keeps its SIMD from the hash to the last line, so no
-        // second dispatch waits behind the randomisation's waves.  With c_early: ciphertexts [0, c_early) first
-        // (one decode + hash lane each, then their line sets on the five-lane kernel, then the census, all on the
-        // preparation stream), the rest [c_early, n_cts) beside them on the second and third streams.
-        uint8_t *hok = (uint8_t *)c->rlc[18].get(n_cts);
-        if (!hok) { set_err("device allocation failed"); return -1; }
-        const u32 nc = (u32)n_cts;
-        if (one_hi) {
-            // fork mode 4: both lane kinds in one dispatch on the context's one high-priority stream, then the census
-            // behind it on the same stream; a context holds one queue per priority, so three batches in flight fit
-            // the box's GPU_MAX_HW_QUEUES = 4
-            lcbk_tpke_ct_prepare_hw(sp, d_u, d_w, d_v, d_voff, nc, lines, hok, ctok, ctg2, fl);
-            hipEventRecord(c->prep_ev[2], sp);
-            if (n && rlc_points_enqueue(c, w, d_accept, n, n_keys, n_cts, d_ct, d_dec, d_ui, sr)) return -1;
-            lcbk_ct_ok_merge(sp, ctok, hok, 0, nc);
-            lines_flag_enqueue(c, 1, lines, 0, nc, sp);
-            c->unn_census = 1;
-        } else {
-        if (!split_ready(c)) return -1;
-        hipStreamWaitEvent(c->hi2, c->fork_ev[0], 0);
-        hipStreamWaitEvent(c->hi3, c->fork_ev[0], 0);
-        const u32 ce = c_early;
-        c->unn_census = ce ? 0 : 1;
-        if (ce) {                    // the census's ciphertexts (decode + hash per lane launched above): their
-                                     // line sets on the five-lane kernel
-            lcbk_lineset_coop_2w(sp, lines, 2 * ce, nullptr, ctg2);   // (2 ce <= 8192 sets: lines_fill's coop range)
-            lines_flag_enqueue(c, 0, lines, 0, ce, sp);
-        }
-        lcbk_tpke_ct_prepare_h(c->hi2, d_u, d_v, d_voff, ce, nc, lines, hok, fl);
-        lcbk_tpke_ct_prepare_w(c->hi3, d_u, d_w, ce, nc, lines, ctok, ctg2, fl);
-        hipEventRecord(c->prep_ev[2], c->hi2);
-        if (n && rlc_points_enqueue(c, w, d_accept, n, n_keys, n_cts, d_ct, d_dec, d_ui, sr)) return -1;
-        hipEventRecord(c->fork_ev[2], c->hi2);
-        hipStreamWaitEvent(c->hi3, c->fork_ev[2], 0);
-        lcbk_ct_ok_merge(c->hi3, ctok, hok, ce, nc);
-        lines_flag_enqueue(c, 1, lines, ce, nc, c->hi3);
-        hipEventRecord(c->fork_ev[3], c->hi3);
-        if (!ce) hipStreamWaitEvent(sp, c->fork_ev[3], 0);     // the census (below) needs every ciphertext
-        }
-    } else if (n_cts) {
-        lcbk_tpke_ct_prepare(dim3(nblk(n_cts)), sp, d_u, d_w, d_v, d_voff, (u32)n_cts, lines, ctok,
-                             g_orig_cofactor | (g_line_mode << 1), nullptr);
-        if (hp) hipEventRecord(c->prep_ev[2], sp);
-        if (prep_first && n && rlc_points_enqueue(c, w, d_accept, n, n_keys, n_cts, d_ct, d_dec, d_ui, sr)) return -1;
-        lines_fill(sp, lines, 2 * n_cts, nullptr, ctg2);
-        c->unn_census = 1;
-        lines_flag_enqueue(c, 1, lines, 0, (u32)n_cts, sp);
-    }
-    if (!launched("tpke prepare launch")) return -1;
-    c->t_n_cts = n_cts;
-    c->t_n_keys = n_keys;
-    c->t_gen++;
-    c->t_ready = true;
-    if (n && rlc_census(c, RLC_TPKE, w, d_accept, io, sp)) return -1;
-    if (n_cts && split && c_early) hipStreamWaitEvent(sp, c->fork_ev[3], 0);   // the bulk's preparation
-    if (hp) {
-        hipEventRecord(c->prep_ev[1], sp);
-        c->prep_timed = true;
-        hipEventRecord(c->fork_ev[1], sp);
-        hipStreamWaitEvent(s, c->fork_ev[1], 0);
-    } else if (n) {
-        hipStreamWaitEvent(s, c->fork_ev[1], 0);
-    }
-    if (!n) return 0;
-    return rlc_levels(c, RLC_TPKE, w, d_accept, n, io, s);
-}
 
 // ------------------------------------------------------------------ threshold signatures
 int ts_prepare(lcb_ctx *c, const uint8_t *d_pks, size_t n_pks, const uint8_t *d_msg, const uint32_t *d_moff,
@@ -1970,8 +1232,7 @@ int ts_prepare(lcb_ctx *c, const uint8_t *d_pks, size_t n_pks, const uint8_t *d_
     void *keys = c->s_keys.get(n_pks * LCB_G1A_ST_BYTES);
     if (!lines || !mok || !keys) { set_err("device allocation failed"); return -1; }
     if (n_pks) lcbk_g1_decompress(dim3(nblk(n_pks)), s, d_pks, (u32)n_pks, keys);
-    if (n_msgs) lcbk_ts_msg_prepare(dim3(nblk(n_msgs)), s, d_msg, d_moff, (u32)n_msgs, lines, mok,
-                                      g_orig_cofactor | (g_line_mode << 1));
+    if (n_msgs) lcbk_ts_msg_prepare(dim3(nblk(n_msgs)), s, d_msg, d_moff, (u32)n_msgs, lines, mok, prepare_flags());
     if (!launched("ts prepare launch")) return -1;
     c->s_n_msgs = n_msgs;
     c->s_n_pks = n_pks;
@@ -1981,11 +1242,7 @@ int ts_prepare(lcb_ctx *c, const uint8_t *d_pks, size_t n_pks, const uint8_t *d_
 }
 int ts_verify_prepared(lcb_ctx *c, uint8_t *d_accept, size_t n, size_t n_pks, size_t n_msgs, const uint8_t *d_sigs,
                        const uint32_t *d_midx, const uint32_t *d_pidx, hipStream_t s) {
-    if (!c->s_ready) { set_err("ts verify: no threshold-signature batch prepared in this context"); return -1; }
-    if (c->s_n_msgs != n_msgs || c->s_n_pks != n_pks) {
-        set_err("ts verify: batch shape differs from the one prepared in this context");
-        return -1;
-    }
+    if (!ts_shape_ok(c, n_pks, n_msgs, "ts verify")) return -1;
     if (n > 0xffffffffu) { set_err("ts verify: batch too large"); return -1; }
     const u32 *lines = (const u32 *)c->s_lines.p;
     const uint8_t *mok = (const uint8_t *)c->s_mok.p;
@@ -2001,86 +1258,6 @@ int ts_verify_prepared(lcb_ctx *c, uint8_t *d_accept, size_t n, size_t n_pks, si
         }
     }
     return launched("ts verify launch") ? 0 : -1;
-}
-
-bool ts_shape_ok(lcb_ctx *c, size_t n_pks, size_t n_msgs, const char *what) {
-    if (!c->s_ready) { set_err((std::string(what) + ": no threshold-signature batch prepared in this context").c_str()); return false; }
-    if (c->s_n_msgs != n_msgs || c->s_n_pks != n_pks) {
-        set_err((std::string(what) + ": batch shape differs from the one prepared in this context").c_str());
-        return false;
-    }
-    return true;
-}
-// randomized batch form of ts_verify_prepared (k_batch.hip): groups = runs of one message (<= 128 shares)
-int ts_verify_prepared_rlc(lcb_ctx *c, uint8_t *d_accept, size_t n, size_t n_pks, size_t n_msgs, const uint8_t *d_sigs,
-                           const uint32_t *d_midx, const uint32_t *d_pidx, hipStream_t s) {
-    if (!ts_shape_ok(c, n_pks, n_msgs, "ts batched verify")) return -1;
-    if (n > 0xffffffffu) { set_err("ts batched verify: batch too large"); return -1; }
-    c->rlc_nlev = 0;
-    if (!n) return 0;
-    RlcWs w;
-    const RlcIo io{d_pidx, d_sigs, d_midx};
-    if (!rlc_ws(c, w, n, LCB_G1_JAC_BYTES, LCB_G2_JAC_BYTES, n_pks, census_size(n, n_pks), s)) return -1;
-    if (rlc_census(c, RLC_TS, w, d_accept, io, s)) return -1;
-    if (ts_rlc_points_enqueue(c, w, d_accept, n, n_pks, n_msgs, d_sigs, d_midx, d_pidx, s)) return -1;
-    return rlc_levels(c, RLC_TS, w, d_accept, n, io, s);
-}
-// prepare + batched verify: the randomisation (keys only) beside the message hashing and the census on the second
-// stream
-int ts_verify_shares_rlc_fused(lcb_ctx *c, uint8_t *d_accept, size_t n, const uint8_t *d_pks, size_t n_pks,
-                               const uint8_t *d_sigs, const uint8_t *d_msg, const uint32_t *d_moff, size_t n_msgs,
-                               const uint32_t *d_midx, const uint32_t *d_pidx, hipStream_t s) {
-    if (n_msgs > 0xffffffffu || n_pks > 0xffffffffu || n > 0xffffffffu) { set_err("ts batched verify: batch too large"); return -1; }
-    c->s_ready = false;
-    c->rlc_nlev = 0;
-    u32 *lines = (u32 *)c->s_lines.get((size_t)n_msgs * LCB_LINESET_BYTES);
-    uint8_t *mok = (uint8_t *)c->s_mok.get(n_msgs);
-    void *keys = c->s_keys.get(n_pks * LCB_G1A_ST_BYTES);
-    if (!lines || !mok || !keys) { set_err("device allocation failed"); return -1; }
-    if (!fork_ready(c)) return -1;
-    if (n_pks) lcbk_g1_decompress(dim3(nblk(n_pks)), s, d_pks, (u32)n_pks, keys);
-    RlcWs w;
-    const RlcIo io{d_pidx, d_sigs, d_midx};
-    // stream layout as in tpke_verify_shares_rlc_fused (lcb_set_fork_mode; 2 acts as 1 here)
-    const bool hp = g_fork_mode.load() >= 1;
-    if (!hp && !aux_ready(c)) return -1;
-    hipStream_t sr = hp ? s : c->aux, sp = hp ? c->hi : s;
-    if (n) {
-        if (!rlc_ws(c, w, n, LCB_G1_JAC_BYTES, LCB_G2_JAC_BYTES, n_pks, census_size(n, n_pks), s)) return -1;
-        keys_first_tables(c, w, keys, n_pks, n, s);
-        hipEventRecord(c->fork_ev[0], s);
-        hipStreamWaitEvent(hp ? sp : sr, c->fork_ev[0], 0);
-        if (hp) hipEventRecord(c->prep_ev[0], sp);
-    } else if (hp) {
-        hipEventRecord(c->fork_ev[0], s);
-        hipStreamWaitEvent(sp, c->fork_ev[0], 0);
-        hipEventRecord(c->prep_ev[0], sp);
-    }
-    // the message preparation (latency-bound, one lane per message) is enqueued ahead of the randomisation, so its
-    // waves take their SIMD slots before the randomisation's fill the device (round 5: enqueued after it, the
-    // preparation ran 462 ms beside a 447 ms randomisation and the census chain waited for it)
-    if (n_msgs) lcbk_ts_msg_prepare(dim3(nblk(n_msgs)), sp, d_msg, d_moff, (u32)n_msgs, lines, mok,
-                                    g_orig_cofactor | (g_line_mode << 1));
-    if (n) {
-        if (ts_rlc_points_enqueue(c, w, d_accept, n, n_pks, n_msgs, d_sigs, d_midx, d_pidx, sr)) return -1;
-        if (!hp) hipEventRecord(c->fork_ev[1], sr);
-    }
-    if (!launched("ts prepare launch")) return -1;
-    c->s_n_msgs = n_msgs;
-    c->s_n_pks = n_pks;
-    c->s_gen++;
-    c->s_ready = true;
-    if (n && rlc_census(c, RLC_TS, w, d_accept, io, sp)) return -1;
-    if (hp) {
-        hipEventRecord(c->prep_ev[1], sp);
-        c->prep_timed = true;
-        hipEventRecord(c->fork_ev[1], sp);
-        hipStreamWaitEvent(s, c->fork_ev[1], 0);
-    } else if (n) {
-        hipStreamWaitEvent(s, c->fork_ev[1], 0);
-    }
-    if (!n) return 0;
-    return rlc_levels(c, RLC_TS, w, d_accept, n, io, s);
 }
 
 // ------------------------------------------------------------------ Lagrange / assembly
@@ -2312,124 +1489,10 @@ extern "C" int lcb_ctx_tpke_verify_phase_ms(lcb_ctx *ctx, float ms[2]) {
         if (hipEventElapsedTime(&ms[i], c->ver_ev[i], c->ver_ev[i + 1]) != hipSuccess) ms[i] = -1.0f;
     return 0;
 }
-
-extern "C" int lcb_ctx_tpke_verify_prepared_batched_dev(lcb_ctx *ctx, uint8_t *accept, size_t n, size_t n_keys,
-                                                        size_t n_cts, const uint32_t *ct_idx, const uint32_t *dec_idx,
-                                                        const uint8_t *ui, void *stream) {
-    CTX_OR(c, ctx, -1)
-    Enq q(c, (hipStream_t)stream);
-    return tpke_verify_prepared_rlc(c, accept, n, n_keys, n_cts, ct_idx, dec_idx, ui, q.s);
-}
-extern "C" int lcb_ctx_tpke_verify_shares_batched_dev(lcb_ctx *ctx, uint8_t *accept, size_t n, const uint8_t *y_keys,
-                                                      size_t n_keys, const uint8_t *cts_u, const uint8_t *cts_w,
-                                                      const uint8_t *v_data, const uint32_t *v_off, size_t n_cts,
-                                                      const uint32_t *ct_idx, const uint32_t *dec_idx,
-                                                      const uint8_t *ui, void *stream) {
-    CTX_OR(c, ctx, -1)
-    Enq q(c, (hipStream_t)stream);
-    return tpke_verify_shares_rlc_fused(c, accept, n, y_keys, n_keys, cts_u, cts_w, v_data, v_off, n_cts, ct_idx,
-                                        dec_idx, ui, q.s);
-}
-extern "C" int lcb_tpke_verify_shares_batched_dev(uint8_t *accept, size_t n, const uint8_t *y_keys, size_t n_keys,
-                                                  const uint8_t *cts_u, const uint8_t *cts_w, const uint8_t *v_data,
-                                                  const uint32_t *v_off, size_t n_cts, const uint32_t *ct_idx,
-                                                  const uint32_t *dec_idx, const uint8_t *ui, void *stream) {
-    return lcb_ctx_tpke_verify_shares_batched_dev(nullptr, accept, n, y_keys, n_keys, cts_u, cts_w, v_data, v_off,
-                                                  n_cts, ct_idx, dec_idx, ui, stream);
-}
-extern "C" int lcb_tpke_verify_prepared_batched_dev(uint8_t *accept, size_t n, size_t n_keys, size_t n_cts,
-                                                    const uint32_t *ct_idx, const uint32_t *dec_idx, const uint8_t *ui,
-                                                    void *stream) {
-    return lcb_ctx_tpke_verify_prepared_batched_dev(nullptr, accept, n, n_keys, n_cts, ct_idx, dec_idx, ui, stream);
-}
-extern "C" int lcb_ctx_tpke_batched_stats(lcb_ctx *ctx, uint32_t levels[8], float ms[6]) {
-    CTX_OR(c, ctx, -1)
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (!c->rlc_ran) { set_err("tpke batched verify: none has run in this context"); return -1; }
-    if (hipEventSynchronize(c->rlc_ev[2]) != hipSuccess) { set_err("tpke batched verify: event sync"); return -1; }
-    for (int i = 0; i < 8; i++) levels[i] = i < c->rlc_nlev ? c->rlc_levels[i] : 0;
-    for (int i = 0; i < 2; i++)
-        if (hipEventElapsedTime(&ms[i], c->rlc_ev[i], c->rlc_ev[i + 1]) != hipSuccess) ms[i] = -1.0f;
-    for (int i = 0; i < 4; i++) ms[2 + i] = c->rlc_ms[i];
-    return c->rlc_nlev;
-}
-extern "C" int lcb_tpke_batched_stats(uint32_t levels[8], float ms[6]) {
-    const RlcStats &st = t_rlc_stats;
-    if (!st.valid) { set_err("batched verify: none has completed on this thread"); return -1; }
-    for (int i = 0; i < 8; i++) levels[i] = st.levels[i];
-    for (int i = 0; i < 6; i++) ms[i] = st.ms[i];
-    return st.nlev;
-}
-extern "C" void lcb_set_batch_seed(const uint8_t *seed32) {
-    // test hook: a fixed ChaCha key makes the batch exponents predictable, so it is honoured only when the process
-    // opted in (LCB_ALLOW_FIXED_BATCH_SEED=1); otherwise the call is ignored and the exponents stay secret
-    const char *e = getenv("LCB_ALLOW_FIXED_BATCH_SEED");
-    std::lock_guard<std::mutex> lk(g_seed_mu);
-    if (seed32 && e && e[0] == '1') { memcpy(g_rlc_seed, seed32, 32); g_rlc_seed_set = true; }
-    else g_rlc_seed_set = false;
-}
-extern "C" void lcb_set_batch_census(size_t min_shares) { g_census_min.store(min_shares); }
-extern "C" int lcb_set_coop_max(uint32_t max_checks) {
-    if (!tuning_allowed("lcb_set_coop_max")) return -1;
-    g_coop_max.store(max_checks);
-    g_coop_miller_max.store(max_checks);
-    return 0;
-}
-extern "C" int lcb_set_fe_pair_min(uint32_t min_entries) {
-    if (!tuning_allowed("lcb_set_fe_pair_min")) return -1;
-    g_fe_pair_min.store(min_entries);
-    return 0;
-}
-extern "C" int lcb_set_busy_coop_max(uint32_t max_checks) {
-    if (!tuning_allowed("lcb_set_busy_coop_max")) return -1;
-    g_busy_coop_max.store(max_checks);
-    return 0;
-}
-extern "C" uint32_t lcb_busy_coop_max(void) { return g_busy_coop_max.load(); }
-extern "C" int lcb_set_level_mode(int mode) {
-    if (!tuning_allowed("lcb_set_level_mode")) return -1;
-    if (mode < 0 || mode > 2) { set_err("lcb_set_level_mode: 0 (by the count), 1 (never busy), 2 (always busy)"); return -1; }
-    g_level_mode.store(mode);
-    return 0;
-}
-extern "C" int lcb_batched_inflight(int device) {
-    if (device < 0 || device >= 64) { set_err("lcb_batched_inflight: device out of range"); return -1; }
-    return (int)g_batched_inflight[device].load();
-}
-extern "C" int lcb_ctx_tpke_level_kernel_stats(lcb_ctx *ctx, uint32_t out[4]) {
-    CTX_OR(c, ctx, -1)
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (!c->rlc_ran) { set_err("tpke batched verify: none has run in this context"); return -1; }
-    for (int i = 0; i < 4; i++) out[i] = c->lvl_kernel[i];
-    return 0;
-}
-extern "C" int lcb_ctx_tpke_fe_pair_stats(lcb_ctx *ctx, uint32_t out[4]) {
-    CTX_OR(c, ctx, -1)
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (!c->rlc_ran) { set_err("tpke batched verify: none has run in this context"); return -1; }
-    for (int i = 0; i < 4; i++) out[i] = c->fe_pair[i];
-    return 0;
-}
-extern "C" int lcb_tpke_fe_pair_stats(uint32_t out[4]) {
-    const RlcStats &st = t_rlc_stats;
-    if (!st.valid) { set_err("batched verify: none has completed on this thread"); return -1; }
-    for (int i = 0; i < 4; i++) out[i] = st.fe_pair[i];
-    return 0;
-}
 extern "C" int lcb_set_verify_chunk(size_t checks) {
     if (!tuning_allowed("lcb_set_verify_chunk")) return -1;
     if (checks == 0 || checks > ((size_t)1 << 21)) { set_err("lcb_set_verify_chunk: 1 .. 2^21"); return -1; }
     g_verify_chunk.store(checks);
-    return 0;
-}
-extern "C" int lcb_set_coop_miller_max(uint32_t max_checks) {
-    if (!tuning_allowed("lcb_set_coop_miller_max")) return -1;
-    g_coop_miller_max.store(max_checks);
-    return 0;
-}
-extern "C" int lcb_set_fork_mode(int mode) {
-    if (!tuning_allowed("lcb_set_fork_mode")) return -1;
-    g_fork_mode.store(mode >= 1 && mode <= 4 ? mode : 0);
     return 0;
 }
 extern "C" int lcb_set_wave_priority(int on) {
@@ -2441,11 +1504,6 @@ extern "C" int lcb_set_wave_priority(int on) {
 extern "C" int lcb_set_msm_segments(int max_segments) {
     if (!tuning_allowed("lcb_set_msm_segments")) return -1;
     g_msm_segs.store(max_segments > 0 ? max_segments : 0);
-    return 0;
-}
-extern "C" int lcb_set_keys_first(int on) {
-    if (!tuning_allowed("lcb_set_keys_first")) return -1;
-    g_keys_first.store(on ? 1 : 0);
     return 0;
 }
 extern "C" int lcb_set_lines_coop_max(int max_sets) {
@@ -2617,19 +1675,6 @@ extern "C" int lcb_debug_tpke_miller(uint32_t *f_out, uint8_t *ok_out, size_t n,
         for (int w = 0; w < 144; w++) f_out[144 * i + w] = soa[((size_t)(w >> 2) * n + i) * 4 + (w & 3)];
     return 0;
 }
-extern "C" int lcb_ctx_batched_census(lcb_ctx *ctx, uint32_t out[4]) {
-    CTX_OR(c, ctx, -1)
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (!c->rlc_ran) { set_err("batched verify: none has run in this context"); return -1; }
-    for (int i = 0; i < 4; i++) out[i] = c->rlc_census[i];
-    return 0;
-}
-extern "C" int lcb_batched_census(uint32_t out[4]) {
-    const RlcStats &st = t_rlc_stats;
-    if (!st.valid) { set_err("batched verify: none has completed on this thread"); return -1; }
-    for (int i = 0; i < 4; i++) out[i] = st.census[i];
-    return 0;
-}
 
 extern "C" int lcb_tpke_prepare_dev(const uint8_t *y_keys, size_t n_keys, const uint8_t *cts_u, const uint8_t *cts_w,
                                     const uint8_t *v_data, const uint32_t *v_off, size_t n_cts, void *stream) {
@@ -2709,7 +1754,7 @@ extern "C" int lcb_tpke_verify_shares_cached(uint8_t *accept, size_t n, const ui
     }
     Enq q(c, c->stream);
     hipStream_t s = c->stream;
-    const int flags = g_orig_cofactor | (g_line_mode << 1);
+    const int flags = prepare_flags();
     if (c->cc_used.empty() || c->cc_flags != flags) {           // first use, or prepare flags changed: empty cache
         c->cc_map.clear();
         c->cc_keys.assign(LCB_CT_CACHE, std::string());
@@ -2954,33 +1999,6 @@ extern "C" int lcb_ts_verify_shares_dev(uint8_t *accept, size_t n, const uint8_t
     if (ts_prepare(c, pks, n_pks, msg_data, msg_off, n_msgs, q.s)) return -1;
     return ts_verify_prepared(c, accept, n, n_pks, n_msgs, sigs, msg_idx, pk_idx, q.s);
 }
-extern "C" int lcb_ctx_ts_verify_prepared_batched_dev(lcb_ctx *ctx, uint8_t *accept, size_t n, size_t n_pks,
-                                                      size_t n_msgs, const uint8_t *sigs, const uint32_t *msg_idx,
-                                                      const uint32_t *pk_idx, void *stream) {
-    CTX_OR(c, ctx, -1)
-    Enq q(c, (hipStream_t)stream);
-    return ts_verify_prepared_rlc(c, accept, n, n_pks, n_msgs, sigs, msg_idx, pk_idx, q.s);
-}
-extern "C" int lcb_ts_verify_prepared_batched_dev(uint8_t *accept, size_t n, size_t n_pks, size_t n_msgs,
-                                                  const uint8_t *sigs, const uint32_t *msg_idx, const uint32_t *pk_idx,
-                                                  void *stream) {
-    return lcb_ctx_ts_verify_prepared_batched_dev(nullptr, accept, n, n_pks, n_msgs, sigs, msg_idx, pk_idx, stream);
-}
-extern "C" int lcb_ctx_ts_verify_shares_batched_dev(lcb_ctx *ctx, uint8_t *accept, size_t n, const uint8_t *pks,
-                                                    size_t n_pks, const uint8_t *sigs, const uint8_t *msg_data,
-                                                    const uint32_t *msg_off, size_t n_msgs, const uint32_t *msg_idx,
-                                                    const uint32_t *pk_idx, void *stream) {
-    CTX_OR(c, ctx, -1)
-    Enq q(c, (hipStream_t)stream);
-    return ts_verify_shares_rlc_fused(c, accept, n, pks, n_pks, sigs, msg_data, msg_off, n_msgs, msg_idx, pk_idx, q.s);
-}
-extern "C" int lcb_ts_verify_shares_batched_dev(uint8_t *accept, size_t n, const uint8_t *pks, size_t n_pks,
-                                                const uint8_t *sigs, const uint8_t *msg_data, const uint32_t *msg_off,
-                                                size_t n_msgs, const uint32_t *msg_idx, const uint32_t *pk_idx,
-                                                void *stream) {
-    return lcb_ctx_ts_verify_shares_batched_dev(nullptr, accept, n, pks, n_pks, sigs, msg_data, msg_off, n_msgs,
-                                                msg_idx, pk_idx, stream);
-}
 static int ts_verify_shares_host(uint8_t *accept, size_t n, const uint8_t *pks, size_t n_pks, const uint8_t *sigs,
                                  const uint8_t *msg_data, const uint32_t *msg_off, size_t n_msgs,
                                  const uint32_t *msg_idx, const uint32_t *pk_idx, bool batched) {
@@ -3073,7 +2091,11 @@ int g1_any_off_subgroup(lcb_ctx *c, const void *d_aff, size_t n, hipStream_t s, 
     hipMemsetAsync(d, 0, 4, s);
     if (n) lcbk_g1_subgroup_any(s, d_aff, (u32)n, d);
     u32 h = 0;
-    if (!launched("subgroup test launch") || !read_counts(&h, d, 1, s)) return -1;
+    if (!launched("subgroup test launch")) return -1;
+    if (hipMemcpyAsync(&h, d, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        set_err("batched verify: group count");
+        return -1;
+    }
     *any = h != 0;
     return 0;
 }
