@@ -28,7 +28,7 @@ extern "C" __global__ void LCB_BOUNDS k_mcl_g1_terms(const g1 *pts, const fr *sc
 }
 
 // terms[i] = [e_i] P_i with 384-bit scalars (12 words each): mclBn_G1EvaluatePolynomial's e_i = x^i mod #E(Fp), so
-// sum_i [e_i] c_i is the Horner value sum_i [x^i] c_i for every on-curve coefficient (lcb_host.cpp eval_poly)
+// sum_i [e_i] c_i is the Horner value sum_i [x^i] c_i for every on-curve coefficient (lcb_mcl.cpp eval_poly)
 extern "C" __global__ void LCB_BOUNDS k_mcl_g1_terms_wide(const g1 *pts, const u32 *scal, u32 n, g1 *terms, u32 *ws) {
     const u32 gid = blockIdx.x * blockDim.x + threadIdx.x, gsz = gridDim.x * blockDim.x;
     char *slot = lw_slot(ws, LW_WIN4_QUADS(fp), gid);

@@ -12,7 +12,7 @@
 //     temporaries) and a ROUND is one Fp (G1) or Fp2 (G2) product per lane on operands it selects by its role, then the
 //     four products are exchanged through LDS.  dbl-2009-l takes 3 rounds instead of 7 serial products, add-2007-bl 5
 //     instead of 16 (the formulas, special cases and results of curve.hpp's jac_dbl / jac_add exactly).
-// The host splits the scalar (lcb_host.cpp): G1 by GLV (k P = k1 P + k2 phi(P), 129-bit halves), each half cut at
+// The host splits the scalar (lcb_mcl.cpp): G1 by GLV (k P = k1 P + k2 phi(P), 129-bit halves), each half cut at
 // bit 65 over P and [2^65] P (four groups of 18 windows); G2 by GLS (four 64-bit digits over +-psi^i(Q)), each digit
 // cut at bit 32 over +-psi^i(Q) and +-psi^i([2^32] Q) (eight groups of 9 windows).  The host computes the [2^65] /
 // [2^32] multiples and the membership test the split needs ([z^2] P == (beta^2 x, -y), psi(Q) == -[|z|] Q) with its
@@ -28,7 +28,7 @@ LCB_TU_CONFIG(k_ptmul)
 #define PT_MAX_WIN 33              // signed 4-bit windows (129-bit GLV halves; 17 for the 64-bit GLS digits)
 
 // one group's job: affine base point (inf = 1: the point at infinity) and nwin signed digits, most significant
-// first, one byte each: |digit| (<= 8) in bits 0-3, bit 7 set for a negative digit (lcb_host.cpp put_digits)
+// first, one byte each: |digit| (<= 8) in bits 0-3, bit 7 set for a negative digit (lcb_mcl.cpp put_digits)
 template <class F> struct PtJob {
     F x, y;
     u32 inf, nwin, pad[2];
@@ -86,7 +86,7 @@ extern "C" __global__ void __launch_bounds__(64, 1) k_ptmul_g2(const PtJob<fp2> 
     __shared__ PtLds<fp2> lds[PT_MAX_GROUPS + 1];
     pt_ladder(jobs, n_groups, out, lds);
 }
-// many G1 ladders at once (mclBnG1_mulVec, mclBn_G1LagrangeInterpolation: three groups per term, lcb_host.cpp
+// many G1 ladders at once (mclBnG1_mulVec, mclBn_G1LagrangeInterpolation: three groups per term, lcb_mcl.cpp
 // g1_mulvec_coop): block b runs groups [16 b, 16 b + 16), every group of a wave with its own LDS area
 #define PT_MULTI_GROUPS 16
 extern "C" __global__ void __launch_bounds__(64, 1) k_ptmul_g1_multi(const PtJob<fp> *jobs, u32 n_groups, g1 *out) {

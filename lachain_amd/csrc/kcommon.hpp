@@ -53,7 +53,7 @@ DI void fp12_load_soa_fresh(fp12 &f, const u32 *base, size_t n, size_t i) {
 }
 
 // per-unit configuration setter (curve.hpp lcb_g2_sign_b): one per kernel translation unit, called by
-// lcbk_set_g2_sign_b (lcb_host.cpp) for every unit
+// lcbk_set_g2_sign_b (lcb_mcl.cpp) for every unit
 #define LCB_TU_CONFIG(tag)                                                                                        \
     extern "C" int lcbk_cfg_##tag(u32 sign_b) {                                                                 \
         return hipMemcpyToSymbol(HIP_SYMBOL(lcb_g2_sign_b), &sign_b, sizeof sign_b) == hipSuccess ? 0 : -1;     \

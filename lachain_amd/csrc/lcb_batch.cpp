@@ -140,7 +140,7 @@ bool rlc_key_fill(lcb_ctx *c, u32 key[10]) {
         fixed = g_rlc_seed_set;
         if (fixed) memcpy(key, g_rlc_seed, 32);
     }
-    if (!fixed && getrandom(key, 32, 0) != 32) { set_error("batched verify: getrandom failed"); return false; }
+    if (!fixed && getrandom(key, 32, 0) != 32) { set_err("batched verify: getrandom failed"); return false; }
     c->rlc_calls++;
     key[8] = (u32)c->rlc_calls;
     key[9] = (u32)(c->rlc_calls >> 32);
@@ -164,7 +164,7 @@ bool rlc_ws(lcb_ctx *c, RlcWs &w, size_t n, size_t rec_a, size_t rec_b, size_t n
     const size_t sw = (n_keys + 31) / 32;
     w.susp = m ? (u32 *)c->rlc[RLC_SUSP].get(4 * sw) : nullptr;
     w.m = m;
-    if (!w.rA || !w.rB || !w.dA || !w.dB || !w.cnt || (m && !w.susp)) { set_error("device allocation failed"); return false; }
+    if (!w.rA || !w.rB || !w.dA || !w.dB || !w.cnt || (m && !w.susp)) { set_err("device allocation failed"); return false; }
     if (!c->rlc_ev_ready) {
         for (auto &e : c->rlc_ev) hipEventCreate(&e);
         for (auto &e : c->rlc_lev_ev) hipEventCreate(&e);
@@ -230,7 +230,7 @@ int ts_rlc_points_enqueue(lcb_ctx *c, RlcWs &w, uint8_t *d_accept, size_t n, siz
 }
 bool read_counts(u32 *v, const u32 *d, int k, hipStream_t s) {
     if (hipMemcpyAsync(v, d, 4 * k, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-        set_error("batched verify: group count");
+        set_err("batched verify: group count");
         return false;
     }
     return true;
@@ -374,7 +374,7 @@ bool rlc_fe_pairs(lcb_ctx *c, const uint8_t *desc, u32 *f, u32 m, uint8_t *gacc,
     // count's read
     u32 *park = (u32 *)c->rlc[RLC_PAIR_PARK].get(2 * park_words * 4);
     void *lists = c->rlc[RLC_PAIR_LISTS].get(FePairWs::bytes(jobs));
-    if (!park || !lists) { set_error("device allocation failed (pair stage)"); return false; }
+    if (!park || !lists) { set_err("device allocation failed (pair stage)"); return false; }
     u32 *park2 = park + park_words;
     const FePairWs ws(lists, jobs);
     hipMemsetAsync(ws.cnt, 0, 16, s);
@@ -385,7 +385,7 @@ bool rlc_fe_pairs(lcb_ctx *c, const uint8_t *desc, u32 *f, u32 m, uint8_t *gacc,
     u32 h[H_N] = {};
     if (!launch_ok("batched verify launch") || !read_counts(h, ws.cnt, H_N, s)) return false;
     const u32 n2 = h[H_PASS2];
-    if (n2 > jobs) { set_error("batched verify: pair stage count"); return false; }
+    if (n2 > jobs) { set_err("batched verify: pair stage count"); return false; }
     if (n2) {
         lcbk_fe_pair_gather(s, f, m, ws.list, n2, park2, ws.pacc2);
         fe_dispatch(c, s, park2, n2, ws.pacc2, true);
@@ -413,7 +413,7 @@ bool rlc_checks(lcb_ctx *c, const RlcKindInfo &K, RlcWs &w, const RlcBufs &L, u3
     uint8_t *mfb = nullptr;
     if (!K.ts && last <= coop_ml_max) {
         mfb = (uint8_t *)c->rlc[RLC_MFB].get(std::min<size_t>(full, coop_ml_max));
-        if (!mfb) { set_error("device allocation failed (Miller fallback flags)"); return false; }
+        if (!mfb) { set_err("device allocation failed (Miller fallback flags)"); return false; }
     }
     float t;
     for (size_t o = 0; o < count; o += LCB_VERIFY_CHUNK) {
@@ -468,7 +468,7 @@ int rlc_census(lcb_ctx *c, RlcKind kind, RlcWs &w, uint8_t *d_accept, RlcIo io, 
     L.gex = (uint8_t *)c->rlc[RLC_GEX].get(m);
     L.cval = (uint8_t *)c->rlc[RLC_CVAL].get(m);
     L.f = (u32 *)c->t_f.get((size_t)m * 576 * (size_t)lcbk_fe_slots());
-    if (!L.gpts || !L.gacc || !L.gex || !L.cval || !L.f) { set_error("device allocation failed"); return -1; }
+    if (!L.gpts || !L.gacc || !L.gex || !L.cval || !L.f) { set_err("device allocation failed"); return -1; }
     lcbk_rlc_census_desc(s, io.d_grp, io.d_key, m, (u32)K.n_grp, (u32)K.n_keys, w.dB, d_accept);
     RlcWs cw = w;
     cw.susp = nullptr;                  // the census singles are exact checks whatever the bitmap says
@@ -516,7 +516,7 @@ int rlc_levels(lcb_ctx *c, RlcKind kind, RlcWs &w, uint8_t *d_accept, size_t n, 
         w.susp = nullptr;               // no suspect key: the sums need not test the bitmap
     }
     for (int lev = -1; groups;) {
-        if (lev + 1 > 40) { set_error("batched verify: group splitting did not terminate"); return -1; }
+        if (lev + 1 > 40) { set_err("batched verify: group splitting did not terminate"); return -1; }
         level_open(c, lev, groups);
         const bool first = lev == 0;
         const size_t nf = groups < LCB_VERIFY_CHUNK ? groups : LCB_VERIFY_CHUNK;
@@ -532,7 +532,7 @@ int rlc_levels(lcb_ctx *c, RlcKind kind, RlcWs &w, uint8_t *d_accept, size_t n, 
             if (K.ts) L.wsum = (u32 *)c->rlc[RLC_WSUM].get((size_t)groups * K.wrec);   // (TPKE: formed at level 2)
         }
         if (!L.gpts || !L.gacc || !L.gex || !L.f || (first && (!L.sdesc || !L.gamma || (K.ts && !L.wsum)))) {
-            set_error("device allocation failed");
+            set_err("device allocation failed");
             return -1;
         }
         uint4 *const sdesc = L.sdesc;
@@ -556,7 +556,7 @@ int rlc_levels(lcb_ctx *c, RlcKind kind, RlcWs &w, uint8_t *d_accept, size_t n, 
             L2.gamma = g12;                             // this pass fills the gamma_c rows
             L2.f = (u32 *)c->t_f.get(nf2 * 576 * (size_t)lcbk_fe_slots());
             u32 *open = (u32 *)c->rlc[RLC_OPEN].get((size_t)ns * 4 + 16);
-            if (!L2.gpts || !L2.gacc || !g12 || !L2.f || !open) { set_error("device allocation failed"); return -1; }
+            if (!L2.gpts || !L2.gacc || !g12 || !L2.f || !open) { set_err("device allocation failed"); return -1; }
             timed_sums(c, s, [&] {
                 lcbk_tpke_rlc_wsum2(s, sdesc, ns, nullptr, w.rA, w.rB, (u32)n, io.d_key, (u32)K.n_keys, w.susp, L2.gpts,
                                     nullptr);
@@ -581,7 +581,7 @@ int rlc_levels(lcb_ctx *c, RlcKind kind, RlcWs &w, uint8_t *d_accept, size_t n, 
                 void *dbg = search2b_dump(s, "in", ns, no, gamma, g12, open, d_accept, n);
 #if LCB_SEARCH2B_ASM
                 u32 *s2b_park = (u32 *)c->rlc[RLC_S2B_PARK].get(lcbk_tpke_rlc_search2b_asm_park_bytes(no));
-                if (!s2b_park) { set_error("device allocation failed (level-2 search slots)"); return -1; }
+                if (!s2b_park) { set_err("device allocation failed (level-2 search slots)"); return -1; }
                 lcbk_tpke_rlc_search2b_asm(s, sdesc, ns, no, gamma, g12, open + 4, open, d_accept, w.dB,
                                            w.cnt + CNT_NEXT, io.d_key, (u32)K.n_keys, w.susp, s2b_park);
 #else
@@ -635,7 +635,7 @@ int rlc_levels(lcb_ctx *c, RlcKind kind, RlcWs &w, uint8_t *d_accept, size_t n, 
 int tpke_verify_prepared_rlc(lcb_ctx *c, uint8_t *d_accept, size_t n, size_t n_keys, size_t n_cts, const uint32_t *d_ct,
                              const uint32_t *d_dec, const uint8_t *d_ui, hipStream_t s) {
     if (!tpke_shape_ok(c, n_keys, n_cts, "tpke batched verify")) return -1;
-    if (n > 0xffffffffu) { set_error("tpke batched verify: batch too large"); return -1; }
+    if (n > 0xffffffffu) { set_err("tpke batched verify: batch too large"); return -1; }
     c->rlc_nlev = 0;
     if (!n) return 0;
     RlcWs w;
@@ -654,7 +654,7 @@ bool fork_ready(lcb_ctx *c) {
         if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
     for (auto &ev : c->prep_ev)
         if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e != hipSuccess) { set_error("batched verify: stream creation", e); return false; }
+    if (e != hipSuccess) { set_err("batched verify: stream creation", e); return false; }
     c->fork_ready = true;
     return true;
 }
@@ -662,7 +662,7 @@ bool fork_ready(lcb_ctx *c) {
 bool aux_ready(lcb_ctx *c) {
     if (c->aux) return true;
     hipError_t e = hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking);
-    if (e != hipSuccess) { c->aux = nullptr; set_error("batched verify: stream creation", e); return false; }
+    if (e != hipSuccess) { c->aux = nullptr; set_err("batched verify: stream creation", e); return false; }
     return true;
 }
 // fork mode 3's two more preparation streams, created on first use: HIP hands every stream a hardware queue when it
@@ -674,7 +674,7 @@ bool split_ready(lcb_ctx *c) {
     hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
     if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->hi2, hipStreamNonBlocking, greatest);
     if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->hi3, hipStreamNonBlocking, greatest);
-    if (e != hipSuccess) { set_error("batched verify: stream creation", e); return false; }
+    if (e != hipSuccess) { set_err("batched verify: stream creation", e); return false; }
     return true;
 }
 // The stream layout of the fused calls (lcb_set_fork_mode).  Mode 0: randomisation on the second stream, preparation +
@@ -702,7 +702,7 @@ void join_caller(lcb_ctx *c, hipStream_t s, hipStream_t sp, bool hp, bool shares
 int ts_verify_prepared_rlc(lcb_ctx *c, uint8_t *d_accept, size_t n, size_t n_pks, size_t n_msgs, const uint8_t *d_sigs,
                            const uint32_t *d_midx, const uint32_t *d_pidx, hipStream_t s) {
     if (!ts_shape_ok(c, n_pks, n_msgs, "ts batched verify")) return -1;
-    if (n > 0xffffffffu) { set_error("ts batched verify: batch too large"); return -1; }
+    if (n > 0xffffffffu) { set_err("ts batched verify: batch too large"); return -1; }
     c->rlc_nlev = 0;
     if (!n) return 0;
     RlcWs w;
@@ -723,7 +723,7 @@ int lcb_int::tpke_verify_shares_rlc_fused(lcb_ctx *c, uint8_t *d_accept, size_t 
                                           const uint32_t *d_voff, size_t n_cts, const uint32_t *d_ct,
                                           const uint32_t *d_dec, const uint8_t *d_ui, hipStream_t s) {
     const BatchedInflight counted(c);          // until this call returns: the level driver's overlap rule (fe_one_lane)
-    if (n_cts > 0xffffffffu || n_keys > 0xffffffffu || n > 0xffffffffu) { set_error("tpke batched verify: batch too large"); return -1; }
+    if (n_cts > 0xffffffffu || n_keys > 0xffffffffu || n > 0xffffffffu) { set_err("tpke batched verify: batch too large"); return -1; }
     c->t_ready = false;
     c->unn_set[0] = c->unn_set[1] = false;     // the fallback flags describe the line sets prepared below
     c->rlc_nlev = 0;
@@ -731,7 +731,7 @@ int lcb_int::tpke_verify_shares_rlc_fused(lcb_ctx *c, uint8_t *d_accept, size_t 
     uint8_t *ctok = (uint8_t *)c->t_ctok.get(n_cts);
     void *keys = c->t_keys.get(n_keys * LCB_G1A_ST_BYTES);
     uint8_t *ctg2 = (uint8_t *)c->t_ctg2.get(n_cts);     // from the line sets (k_lineset_fill)
-    if (!lines || !ctok || !keys || !ctg2) { set_error("device allocation failed"); return -1; }
+    if (!lines || !ctok || !keys || !ctg2) { set_err("device allocation failed"); return -1; }
     if (!fork_ready(c)) return -1;
     const int fm = g_fork_mode.load();
     const bool hp = fm >= 1, prep_first = fm >= 2 && n_cts, split = fm >= 3, one_hi = fm == 4;
@@ -743,7 +743,7 @@ int lcb_int::tpke_verify_shares_rlc_fused(lcb_ctx *c, uint8_t *d_accept, size_t 
     if (n_cts && split && !one_hi && m_census) {
         std::vector<uint32_t> ci(m_census);
         if (hipMemcpyAsync(ci.data(), d_ct, 4 * (size_t)m_census, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) { set_error("tpke batched verify: census index read"); return -1; }
+            hipStreamSynchronize(s) != hipSuccess) { set_err("tpke batched verify: census index read"); return -1; }
         u32 mx = 0;
         for (uint32_t x : ci) mx = std::max(mx, x);
         if ((size_t)mx + 1 < n_cts && mx < 4096u) c_early = mx + 1;
@@ -780,7 +780,7 @@ int lcb_int::tpke_verify_shares_rlc_fused(lcb_ctx *c, uint8_t *d_accept, size_t 
         // (one decode + hash lane each, then their line sets on the five-lane kernel, then the census, all on the
         // preparation stream), the rest [c_early, n_cts) beside them on the second and third streams.
         uint8_t *hok = (uint8_t *)c->rlc[RLC_HOK].get(n_cts);
-        if (!hok) { set_error("device allocation failed"); return -1; }
+        if (!hok) { set_err("device allocation failed"); return -1; }
         const u32 nc = (u32)n_cts;
         if (one_hi) {
             // fork mode 4: both lane kinds in one dispatch on the context's one high-priority stream, then the census
@@ -838,13 +838,13 @@ int lcb_int::tpke_verify_shares_rlc_fused(lcb_ctx *c, uint8_t *d_accept, size_t 
 int lcb_int::ts_verify_shares_rlc_fused(lcb_ctx *c, uint8_t *d_accept, size_t n, const uint8_t *d_pks, size_t n_pks,
                                         const uint8_t *d_sigs, const uint8_t *d_msg, const uint32_t *d_moff,
                                         size_t n_msgs, const uint32_t *d_midx, const uint32_t *d_pidx, hipStream_t s) {
-    if (n_msgs > 0xffffffffu || n_pks > 0xffffffffu || n > 0xffffffffu) { set_error("ts batched verify: batch too large"); return -1; }
+    if (n_msgs > 0xffffffffu || n_pks > 0xffffffffu || n > 0xffffffffu) { set_err("ts batched verify: batch too large"); return -1; }
     c->s_ready = false;
     c->rlc_nlev = 0;
     u32 *lines = (u32 *)c->s_lines.get((size_t)n_msgs * LCB_LINESET_BYTES);
     uint8_t *mok = (uint8_t *)c->s_mok.get(n_msgs);
     void *keys = c->s_keys.get(n_pks * LCB_G1A_ST_BYTES);
-    if (!lines || !mok || !keys) { set_error("device allocation failed"); return -1; }
+    if (!lines || !mok || !keys) { set_err("device allocation failed"); return -1; }
     if (!fork_ready(c)) return -1;
     if (n_pks) lcbk_g1_decompress(dim3(nblk(n_pks)), s, d_pks, (u32)n_pks, keys);
     RlcWs w;
@@ -879,10 +879,6 @@ int lcb_int::ts_verify_shares_rlc_fused(lcb_ctx *c, uint8_t *d_accept, size_t n,
 
 // ================================================================== C ABI: the batched entry points on device
 // pointers, their statistics and their knobs (the host-pointer forms are in lcb_host.cpp)
-#define CTX_OR(var, ctxarg, ret)                 \
-    lcb_ctx *var = ctx_resolve(ctxarg);          \
-    if (!var) return ret;
-
 extern "C" int lcb_ctx_tpke_verify_prepared_batched_dev(lcb_ctx *ctx, uint8_t *accept, size_t n, size_t n_keys,
                                                         size_t n_cts, const uint32_t *ct_idx, const uint32_t *dec_idx,
                                                         const uint8_t *ui, void *stream) {
@@ -943,8 +939,8 @@ extern "C" int lcb_ts_verify_shares_batched_dev(uint8_t *accept, size_t n, const
 extern "C" int lcb_ctx_tpke_batched_stats(lcb_ctx *ctx, uint32_t levels[8], float ms[6]) {
     CTX_OR(c, ctx, -1)
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (!c->rlc_ran) { set_error("tpke batched verify: none has run in this context"); return -1; }
-    if (hipEventSynchronize(c->rlc_ev[2]) != hipSuccess) { set_error("tpke batched verify: event sync"); return -1; }
+    if (!c->rlc_ran) { set_err("tpke batched verify: none has run in this context"); return -1; }
+    if (hipEventSynchronize(c->rlc_ev[2]) != hipSuccess) { set_err("tpke batched verify: event sync"); return -1; }
     for (int i = 0; i < 8; i++) levels[i] = i < c->rlc_nlev ? c->rlc_levels[i] : 0;
     for (int i = 0; i < 2; i++)
         if (hipEventElapsedTime(&ms[i], c->rlc_ev[i], c->rlc_ev[i + 1]) != hipSuccess) ms[i] = -1.0f;
@@ -953,7 +949,7 @@ extern "C" int lcb_ctx_tpke_batched_stats(lcb_ctx *ctx, uint32_t levels[8], floa
 }
 extern "C" int lcb_tpke_batched_stats(uint32_t levels[8], float ms[6]) {
     const RlcStats &st = t_rlc_stats;
-    if (!st.valid) { set_error("batched verify: none has completed on this thread"); return -1; }
+    if (!st.valid) { set_err("batched verify: none has completed on this thread"); return -1; }
     for (int i = 0; i < 8; i++) levels[i] = st.levels[i];
     for (int i = 0; i < 6; i++) ms[i] = st.ms[i];
     return st.nlev;
@@ -961,38 +957,38 @@ extern "C" int lcb_tpke_batched_stats(uint32_t levels[8], float ms[6]) {
 extern "C" int lcb_ctx_tpke_level_kernel_stats(lcb_ctx *ctx, uint32_t out[4]) {
     CTX_OR(c, ctx, -1)
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (!c->rlc_ran) { set_error("tpke batched verify: none has run in this context"); return -1; }
+    if (!c->rlc_ran) { set_err("tpke batched verify: none has run in this context"); return -1; }
     for (int i = 0; i < LVL_KERNEL_N; i++) out[i] = c->lvl_kernel[i];
     return 0;
 }
 extern "C" int lcb_ctx_tpke_fe_pair_stats(lcb_ctx *ctx, uint32_t out[4]) {
     CTX_OR(c, ctx, -1)
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (!c->rlc_ran) { set_error("tpke batched verify: none has run in this context"); return -1; }
+    if (!c->rlc_ran) { set_err("tpke batched verify: none has run in this context"); return -1; }
     for (int i = 0; i < FE_PAIR_N; i++) out[i] = c->fe_pair[i];
     return 0;
 }
 extern "C" int lcb_tpke_fe_pair_stats(uint32_t out[4]) {
     const RlcStats &st = t_rlc_stats;
-    if (!st.valid) { set_error("batched verify: none has completed on this thread"); return -1; }
+    if (!st.valid) { set_err("batched verify: none has completed on this thread"); return -1; }
     for (int i = 0; i < FE_PAIR_N; i++) out[i] = st.fe_pair[i];
     return 0;
 }
 extern "C" int lcb_ctx_batched_census(lcb_ctx *ctx, uint32_t out[4]) {
     CTX_OR(c, ctx, -1)
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (!c->rlc_ran) { set_error("batched verify: none has run in this context"); return -1; }
+    if (!c->rlc_ran) { set_err("batched verify: none has run in this context"); return -1; }
     for (int i = 0; i < CENSUS_N; i++) out[i] = c->rlc_census[i];
     return 0;
 }
 extern "C" int lcb_batched_census(uint32_t out[4]) {
     const RlcStats &st = t_rlc_stats;
-    if (!st.valid) { set_error("batched verify: none has completed on this thread"); return -1; }
+    if (!st.valid) { set_err("batched verify: none has completed on this thread"); return -1; }
     for (int i = 0; i < CENSUS_N; i++) out[i] = st.census[i];
     return 0;
 }
 extern "C" int lcb_batched_inflight(int device) {
-    if (device < 0 || device >= 64) { set_error("lcb_batched_inflight: device out of range"); return -1; }
+    if (device < 0 || device >= 64) { set_err("lcb_batched_inflight: device out of range"); return -1; }
     return (int)g_batched_inflight[device].load();
 }
 // ---- knobs
@@ -1028,7 +1024,7 @@ extern "C" int lcb_set_busy_coop_max(uint32_t max_checks) {
 extern "C" uint32_t lcb_busy_coop_max(void) { return g_busy_coop_max.load(); }
 extern "C" int lcb_set_level_mode(int mode) {
     if (!tuning_allowed("lcb_set_level_mode")) return -1;
-    if (mode < 0 || mode > 2) { set_error("lcb_set_level_mode: 0 (by the count), 1 (never busy), 2 (always busy)"); return -1; }
+    if (mode < 0 || mode > 2) { set_err("lcb_set_level_mode: 0 (by the count), 1 (never busy), 2 (always busy)"); return -1; }
     g_level_mode.store(mode);
     return 0;
 }

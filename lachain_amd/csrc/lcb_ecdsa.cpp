@@ -45,18 +45,18 @@ bool build_tables(hipStream_t s, const void *aff, const u32 *ok, size_t n, void 
     size_t tmp_bytes = 2 * 128 * 33 * n * 32;
     void *tmp = nullptr;
     hipError_t e = hipMalloc(&tmp, tmp_bytes);
-    if (e != hipSuccess) { set_error("comb table workspace", e); return false; }
+    if (e != hipSuccess) { set_err("comb table workspace", e); return false; }
     lcbk_secp_comb_build(s, aff, ok, (u32)n, tables, tmp);
     bool good = launch_ok("comb table build");
     e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { set_error("comb table build", e); good = false; }
+    if (e != hipSuccess) { set_err("comb table build", e); good = false; }
     (void)hipFree(tmp);
     return good;
 }
 
 const void *gen_table(hipStream_t s) {
     int dev = device();
-    if (dev < 0 || dev >= 64) { set_error("device index out of range"); return nullptr; }
+    if (dev < 0 || dev >= 64) { set_err("device index out of range"); return nullptr; }
     std::lock_guard<std::mutex> lk(g_gen_mu);
     if (g_gen_table[dev]) return g_gen_table[dev];
     void *aff = nullptr, *tab = nullptr;
@@ -65,7 +65,7 @@ const void *gen_table(hipStream_t s) {
     if (e == hipSuccess) e = hipMalloc(&ok, 4);
     if (e == hipSuccess) e = hipMalloc(&tab, lcbk_secp_table_bytes());
     if (e != hipSuccess) {
-        set_error("generator table allocation", e);
+        set_err("generator table allocation", e);
         if (aff) (void)hipFree(aff);
         if (ok) (void)hipFree(ok);
         if (tab) (void)hipFree(tab);
@@ -81,8 +81,8 @@ const void *gen_table(hipStream_t s) {
 }
 
 lcb_ecdsa_keyset *keyset_new(lcb_ctx *c, const uint8_t *pubkeys, size_t pk_len, size_t n_keys) {
-    if (pk_len != 33 && pk_len != 65) { set_error("ecdsa key set: keys must be 33 (compressed) or 65 bytes"); return nullptr; }
-    if (n_keys == 0 || n_keys > (1u << 20)) { set_error("ecdsa key set: 1 .. 2^20 keys"); return nullptr; }
+    if (pk_len != 33 && pk_len != 65) { set_err("ecdsa key set: keys must be 33 (compressed) or 65 bytes"); return nullptr; }
+    if (n_keys == 0 || n_keys > (1u << 20)) { set_err("ecdsa key set: 1 .. 2^20 keys"); return nullptr; }
     Enq q(c, c->stream);
     if (!gen_table(c->stream)) return nullptr;
     lcb_ecdsa_keyset *ks = new lcb_ecdsa_keyset;
@@ -94,7 +94,7 @@ lcb_ecdsa_keyset *keyset_new(lcb_ctx *c, const uint8_t *pubkeys, size_t pk_len, 
     if (e == hipSuccess) e = hipMalloc(&ks->tables, lcbk_secp_table_bytes() * n_keys);
     if (e == hipSuccess) e = hipMalloc(&dpk, pk_len * n_keys);
     if (e != hipSuccess) {
-        set_error("ecdsa key set allocation", e);
+        set_err("ecdsa key set allocation", e);
         if (dpk) (void)hipFree(dpk);
         keyset_free(ks);
         return nullptr;
@@ -106,7 +106,7 @@ lcb_ecdsa_keyset *keyset_new(lcb_ctx *c, const uint8_t *pubkeys, size_t pk_len, 
     if (good) {
         std::vector<u32> okw(n_keys);
         e = hipMemcpy(okw.data(), ks->ok, 4 * n_keys, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { set_error("ecdsa key set", e); good = false; }
+        if (e != hipSuccess) { set_err("ecdsa key set", e); good = false; }
         ks->ok_host.resize(n_keys);
         for (size_t i = 0; i < n_keys; i++) ks->ok_host[i] = okw[i] != 0;
     }
@@ -119,17 +119,17 @@ int verify_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *accept, const uint8_t *ha
                    uint64_t era, const uint8_t *sigs, size_t sig_len, const int32_t *key_idx, size_t n,
                    const lcb_ecdsa_keyset *ks, int use_new_chain_id, int32_t chain_id) {
     if (!n) return 0;
-    if (!ks) { set_error("ecdsa: null key set"); return -1; }
-    if (ks->device != c->device) { set_error("ecdsa: key set belongs to another device"); return -1; }
-    if (n > 0xffffffffu / 2) { set_error("ecdsa: batch too large"); return -1; }
-    if (sig_len == 0 || sig_len > 4096) { set_error("ecdsa: bad signature stride"); return -1; }
+    if (!ks) { set_err("ecdsa: null key set"); return -1; }
+    if (ks->device != c->device) { set_err("ecdsa: key set belongs to another device"); return -1; }
+    if (n > 0xffffffffu / 2) { set_err("ecdsa: batch too large"); return -1; }
+    if (sig_len == 0 || sig_len > 4096) { set_err("ecdsa: bad signature stride"); return -1; }
     const void *gt = gen_table(s);
     if (!gt) return -1;
     void *jobs = c->ec[0].get(lcbk_secp_job_bytes() * n);
-    if (!jobs) { set_error("device allocation failed"); return -1; }
+    if (!jobs) { set_err("device allocation failed"); return -1; }
     if (!c->ec_ev_ready) {
         for (auto &e : c->ec_ev)
-            if (hipEventCreate(&e) != hipSuccess) { set_error("event creation"); return -1; }
+            if (hipEventCreate(&e) != hipSuccess) { set_err("event creation"); return -1; }
         c->ec_ev_ready = true;
     }
     const uint8_t *pre_ok = nullptr;
@@ -137,7 +137,7 @@ int verify_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *accept, const uint8_t *ha
     c->ec_hashed = hashes == nullptr;
     if (!hashes) {
         uint8_t *h = (uint8_t *)c->ec[1].get(32 * n), *po = (uint8_t *)c->ec[2].get(n);
-        if (!h || !po) { set_error("device allocation failed"); return -1; }
+        if (!h || !po) { set_err("device allocation failed"); return -1; }
         lcbk_secp_header_hash(s, headers, (u32)n, era, h, po);
         hashes = h;
         pre_ok = po;
@@ -185,7 +185,7 @@ int verify_host(uint8_t *accept, const uint8_t *hashes, const uint8_t *headers, 
     uint8_t *din = (uint8_t *)c->ec[3].get(in_bytes), *dsig = (uint8_t *)c->ec[4].get(sig_len * n);
     int32_t *didx = (int32_t *)c->ec[5].get(4 * n);
     uint8_t *dout = (uint8_t *)c->out[0].get(n);
-    if (!din || !dsig || !didx || !dout) { set_error("device allocation failed"); return -1; }
+    if (!din || !dsig || !didx || !dout) { set_err("device allocation failed"); return -1; }
     hipMemcpyAsync(din, headers ? headers : hashes, in_bytes, hipMemcpyHostToDevice, s);
     hipMemcpyAsync(dsig, sigs, sig_len * n, hipMemcpyHostToDevice, s);
     hipMemcpyAsync(didx, key_idx, 4 * n, hipMemcpyHostToDevice, s);
@@ -193,7 +193,7 @@ int verify_host(uint8_t *accept, const uint8_t *hashes, const uint8_t *headers, 
                        use_new_chain_id, chain_id))
         return -1;
     hipMemcpyAsync(accept, dout, n, hipMemcpyDeviceToHost, s);
-    return sync_ok(c, "ecdsa verify") ? 0 : -1;
+    return sync_check(c, "ecdsa verify") ? 0 : -1;
 }
 
 }  // namespace
@@ -225,7 +225,7 @@ extern "C" void lcb_ecdsa_keyset_destroy(lcb_ecdsa_keyset *ks) {
 }
 extern "C" size_t lcb_ecdsa_keyset_size(const lcb_ecdsa_keyset *ks) { return ks ? ks->n_keys : 0; }
 extern "C" int lcb_ecdsa_keyset_valid(const lcb_ecdsa_keyset *ks, uint8_t *ok_out) {
-    if (!ks) { set_error("ecdsa: null key set"); return -1; }
+    if (!ks) { set_err("ecdsa: null key set"); return -1; }
     memcpy(ok_out, ks->ok_host.data(), ks->n_keys);
     return 0;
 }
@@ -252,11 +252,11 @@ extern "C" int lcb_ctx_ecdsa_phase_ms(lcb_ctx *ctx, float ms[3]) {
     lcb_ctx *c = ctx_resolve(ctx);
     if (!c) return -1;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (!c->ec_ran) { set_error("no ECDSA verification has run in this context"); return -1; }
+    if (!c->ec_ran) { set_err("no ECDSA verification has run in this context"); return -1; }
     for (int k = 0; k < 3; k++) {
         hipError_t e = hipEventSynchronize(c->ec_ev[k + 1]);
         if (e == hipSuccess) e = hipEventElapsedTime(&ms[k], c->ec_ev[k], c->ec_ev[k + 1]);
-        if (e != hipSuccess) { set_error("ecdsa phase timing", e); return -1; }
+        if (e != hipSuccess) { set_err("ecdsa phase timing", e); return -1; }
     }
     if (!c->ec_hashed) ms[0] = 0.f;
     return 0;
@@ -294,12 +294,12 @@ extern "C" int lcb_header_keccak_batch(uint8_t *hashes, const lcb_block_header *
     Enq q(c, c->stream);
     hipStream_t s = c->stream;
     uint8_t *dh = (uint8_t *)c->ec[3].get(112 * n), *dout = (uint8_t *)c->ec[1].get(32 * n), *po = (uint8_t *)c->ec[2].get(n);
-    if (!dh || !dout || !po) { set_error("device allocation failed"); return -1; }
+    if (!dh || !dout || !po) { set_err("device allocation failed"); return -1; }
     hipMemcpyAsync(dh, headers, 112 * n, hipMemcpyHostToDevice, s);
     lcbk_secp_header_hash(s, dh, (u32)n, 0, dout, po);
     if (!launch_ok("header hash launch")) return -1;
     hipMemcpyAsync(hashes, dout, 32 * n, hipMemcpyDeviceToHost, s);
-    return sync_ok(c, "header hash") ? 0 : -1;
+    return sync_check(c, "header hash") ? 0 : -1;
 }
 
 // ------------------------------------------------------------------ signing side (key derivation, SignHashed with given
@@ -343,12 +343,12 @@ extern "C" int lcb_ecdsa_pubkey_batch(uint8_t *out33, uint8_t *ok, const uint8_t
     if (!n) return 0;
     Enq q(c, c->stream);
     uint8_t *dp = (uint8_t *)c->ec[3].get(32 * n), *dout = (uint8_t *)c->ec[4].get(34 * n);
-    if (!dp || !dout) { set_error("device allocation failed"); return -1; }
+    if (!dp || !dout) { set_err("device allocation failed"); return -1; }
     hipMemcpyAsync(dp, privs, 32 * n, hipMemcpyHostToDevice, c->stream);
     if (lcb_ctx_ecdsa_pubkey_dev(c, dout, dout + 33 * n, dp, n, c->stream)) return -1;
     hipMemcpyAsync(out33, dout, 33 * n, hipMemcpyDeviceToHost, c->stream);
     hipMemcpyAsync(ok, dout + 33 * n, n, hipMemcpyDeviceToHost, c->stream);
-    return sync_ok(c, "ecdsa pubkey") ? 0 : -1;
+    return sync_check(c, "ecdsa pubkey") ? 0 : -1;
 }
 extern "C" int lcb_ecdsa_sign_hashed_batch(uint8_t *sigs_out, uint8_t *ok, const uint8_t *hashes, const uint8_t *privs,
                                            const uint8_t *nonces, size_t n, int use_new_chain_id, int32_t chain_id) {
@@ -358,7 +358,7 @@ extern "C" int lcb_ecdsa_sign_hashed_batch(uint8_t *sigs_out, uint8_t *ok, const
     Enq q(c, c->stream);
     size_t L = use_new_chain_id ? 66 : 65;
     uint8_t *din = (uint8_t *)c->ec[3].get(96 * n), *dout = (uint8_t *)c->ec[4].get((L + 1) * n);
-    if (!din || !dout) { set_error("device allocation failed"); return -1; }
+    if (!din || !dout) { set_err("device allocation failed"); return -1; }
     hipMemcpyAsync(din, hashes, 32 * n, hipMemcpyHostToDevice, c->stream);
     hipMemcpyAsync(din + 32 * n, privs, 32 * n, hipMemcpyHostToDevice, c->stream);
     hipMemcpyAsync(din + 64 * n, nonces, 32 * n, hipMemcpyHostToDevice, c->stream);
@@ -367,7 +367,7 @@ extern "C" int lcb_ecdsa_sign_hashed_batch(uint8_t *sigs_out, uint8_t *ok, const
         return -1;
     hipMemcpyAsync(sigs_out, dout, L * n, hipMemcpyDeviceToHost, c->stream);
     hipMemcpyAsync(ok, dout + L * n, n, hipMemcpyDeviceToHost, c->stream);
-    return sync_ok(c, "ecdsa sign") ? 0 : -1;
+    return sync_check(c, "ecdsa sign") ? 0 : -1;
 }
 
 // ------------------------------------------------------------------ public-key recovery (transaction senders)
@@ -381,11 +381,11 @@ int recover_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *pub33, uint8_t *addr20, 
                     const uint8_t *hashes, const uint8_t *sigs, size_t sig_len, const uint8_t *from20, size_t n,
                     int special, int use_new_chain_id, int32_t chain_id) {
     if (!n) return 0;
-    if (n > 0xffffffffu / 2) { set_error("ecdsa recover: batch too large"); return -1; }
-    if (sig_len == 0 || sig_len > 4096) { set_error("ecdsa recover: bad signature stride"); return -1; }
+    if (n > 0xffffffffu / 2) { set_err("ecdsa recover: batch too large"); return -1; }
+    if (sig_len == 0 || sig_len > 4096) { set_err("ecdsa recover: bad signature stride"); return -1; }
     if (!c->er_ev_ready) {
         for (auto &e : c->er_ev)
-            if (hipEventCreate(&e) != hipSuccess) { set_error("event creation"); return -1; }
+            if (hipEventCreate(&e) != hipSuccess) { set_err("event creation"); return -1; }
         c->er_ev_ready = true;
     }
     // DefaultCrypto.SignatureSize (DefaultCrypto.cs:26-29); SpecialRecoverSignatureHashed takes 65 bytes
@@ -403,7 +403,7 @@ int recover_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *pub33, uint8_t *addr20, 
     const void *gt = gen_table(s);
     if (!gt) return -1;
     void *jobs = c->er[0].get(lcbk_secp_rjob_bytes() * n), *pts = c->er[1].get(lcbk_secp_rpoint_bytes() * n);
-    if (!jobs || !pts) { set_error("device allocation failed"); return -1; }
+    if (!jobs || !pts) { set_err("device allocation failed"); return -1; }
     (void)hipEventRecord(c->er_ev[0], s);
     lcbk_secp_rec_scalars(s, hashes, sigs, (u32)sig_len, want, chain_id, special, (u32)n, jobs);
     (void)hipEventRecord(c->er_ev[1], s);
@@ -421,14 +421,14 @@ int recover_host(uint8_t *pub33, uint8_t *addr20, uint8_t *ok, uint8_t *accept, 
     lcb_ctx *c = ctx_sync();
     if (!c) return -1;
     if (!n) return 0;
-    if (sig_len == 0 || sig_len > 4096) { set_error("ecdsa recover: bad signature stride"); return -1; }
+    if (sig_len == 0 || sig_len > 4096) { set_err("ecdsa recover: bad signature stride"); return -1; }
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     Enq q(c, c->stream);
     hipStream_t s = c->stream;
     uint8_t *dh = (uint8_t *)c->er[2].get(32 * n), *dsig = (uint8_t *)c->er[3].get(sig_len * n);
     uint8_t *dfrom = from20 ? (uint8_t *)c->er[4].get(20 * n) : nullptr;
     uint8_t *dout = (uint8_t *)c->er[5].get(55 * n);        // 33 key | 20 address | ok | accept
-    if (!dh || !dsig || (from20 && !dfrom) || !dout) { set_error("device allocation failed"); return -1; }
+    if (!dh || !dsig || (from20 && !dfrom) || !dout) { set_err("device allocation failed"); return -1; }
     uint8_t *dpub = dout, *daddr = dout + 33 * n, *dok = dout + 53 * n, *dacc = dout + 54 * n;
     hipMemcpyAsync(dh, hashes, 32 * n, hipMemcpyHostToDevice, s);
     hipMemcpyAsync(dsig, sigs, sig_len * n, hipMemcpyHostToDevice, s);
@@ -440,7 +440,7 @@ int recover_host(uint8_t *pub33, uint8_t *addr20, uint8_t *ok, uint8_t *accept, 
     if (addr20) hipMemcpyAsync(addr20, daddr, 20 * n, hipMemcpyDeviceToHost, s);
     if (ok) hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, s);
     if (accept) hipMemcpyAsync(accept, dacc, n, hipMemcpyDeviceToHost, s);
-    return sync_ok(c, "ecdsa recover") ? 0 : -1;
+    return sync_check(c, "ecdsa recover") ? 0 : -1;
 }
 }  // namespace
 
@@ -466,7 +466,7 @@ extern "C" int lcb_ctx_tx_verify_dev(lcb_ctx *ctx, uint8_t *accept, const uint8_
                                      int32_t chain_id, void *stream) {
     lcb_ctx *c = ctx_resolve(ctx);
     if (!c) return -1;
-    if (n && (!accept || !from20)) { set_error("tx verify: accept and from20 are required"); return -1; }
+    if (n && (!accept || !from20)) { set_err("tx verify: accept and from20 are required"); return -1; }
     Enq q(c, (hipStream_t)stream);
     return recover_enqueue(c, q.s, nullptr, nullptr, nullptr, accept, hashes, sigs, sig_len, from20, n, 0,
                            use_new_chain_id, chain_id);
@@ -499,7 +499,7 @@ extern "C" int lcb_ecdsa_special_recover_hashed_batch(uint8_t *pub33_out, uint8_
 }
 extern "C" int lcb_tx_verify_batch(uint8_t *accept, const uint8_t *hashes, const uint8_t *sigs, size_t sig_len,
                                    const uint8_t *from20, size_t n, int use_new_chain_id, int32_t chain_id) {
-    if (n && (!accept || !from20)) { set_error("tx verify: accept and from20 are required"); return -1; }
+    if (n && (!accept || !from20)) { set_err("tx verify: accept and from20 are required"); return -1; }
     return recover_host(nullptr, nullptr, nullptr, accept, hashes, sigs, sig_len, from20, n, 0, use_new_chain_id,
                         chain_id);
 }
@@ -508,11 +508,11 @@ extern "C" int lcb_ctx_ecdsa_recover_phase_ms(lcb_ctx *ctx, float ms[3]) {
     lcb_ctx *c = ctx_resolve(ctx);
     if (!c) return -1;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (!c->er_ran) { set_error("no ECDSA recovery has run in this context"); return -1; }
+    if (!c->er_ran) { set_err("no ECDSA recovery has run in this context"); return -1; }
     for (int k = 0; k < 3; k++) {
         hipError_t e = hipEventSynchronize(c->er_ev[k + 1]);
         if (e == hipSuccess) e = hipEventElapsedTime(&ms[k], c->er_ev[k], c->er_ev[k + 1]);
-        if (e != hipSuccess) { set_error("ecdsa recover phase timing", e); return -1; }
+        if (e != hipSuccess) { set_err("ecdsa recover phase timing", e); return -1; }
     }
     return 0;
 }
@@ -526,7 +526,7 @@ extern "C" int lcb_ctx_keccak256_dev(lcb_ctx *ctx, uint8_t *out32, const uint8_t
     if (!c) return -1;
     Enq q(c, (hipStream_t)stream);
     if (!n) return 0;
-    if (n > 0xffffffffu / 2) { set_error("keccak256: batch too large"); return -1; }
+    if (n > 0xffffffffu / 2) { set_err("keccak256: batch too large"); return -1; }
     lcbk_keccak256(q.s, data, off, (u32)n, out32);
     return launch_ok("keccak256 launch") ? 0 : -1;
 }
@@ -538,7 +538,7 @@ extern "C" int lcb_keccak256_batch(uint8_t *out32, const uint8_t *data, const ui
     if (!c) return -1;
     if (!n) return 0;
     for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) { set_error("keccak256: offsets must not decrease"); return -1; }
+        if (off[i + 1] < off[i]) { set_err("keccak256: offsets must not decrease"); return -1; }
     size_t bytes = (size_t)(off[n] - off[0]);
     std::vector<uint64_t> rel(n + 1);
     for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
@@ -546,10 +546,10 @@ extern "C" int lcb_keccak256_batch(uint8_t *out32, const uint8_t *data, const ui
     hipStream_t s = c->stream;
     uint8_t *dd = (uint8_t *)c->er[2].get(bytes), *dout = (uint8_t *)c->er[5].get(32 * n);
     uint64_t *doff = (uint64_t *)c->er[3].get(8 * (n + 1));
-    if (!dd || !dout || !doff) { set_error("device allocation failed"); return -1; }
+    if (!dd || !dout || !doff) { set_err("device allocation failed"); return -1; }
     if (bytes) hipMemcpyAsync(dd, data + off[0], bytes, hipMemcpyHostToDevice, s);
     hipMemcpyAsync(doff, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, s);
     if (lcb_ctx_keccak256_dev(c, dout, dd, doff, n, s)) return -1;
     hipMemcpyAsync(out32, dout, 32 * n, hipMemcpyDeviceToHost, s);
-    return sync_ok(c, "keccak256") ? 0 : -1;
+    return sync_check(c, "keccak256") ? 0 : -1;
 }

@@ -26,13 +26,13 @@ namespace {
 enum { W_JOBS, W_PTS, W_KEYS, W_EOK, W_EPH, W_POK, W_OFF, S_PUB, S_SCALAR, S_IDX, S_OUT, S_NONCE, S_DATA, S_KEYS };
 
 bool size_ok(const char *what, size_t n) {
-    if (n > 0xffffffffu / 2) { set_error(what); return false; }
+    if (n > 0xffffffffu / 2) { set_err(what); return false; }
     return true;
 }
 bool events_ready(lcb_ctx *c) {
     if (c->ecies_ev_ready) return true;
     for (auto &e : c->ecies_ev)
-        if (hipEventCreate(&e) != hipSuccess) { set_error("event creation"); return false; }
+        if (hipEventCreate(&e) != hipSuccess) { set_err("event creation"); return false; }
     c->ecies_ev_ready = true;
     return true;
 }
@@ -50,7 +50,7 @@ int ecdh_core(lcb_ctx *c, hipStream_t s, uint8_t *key32, uint8_t *ok, const uint
               u32 min_len, const uint8_t *scalars32, const u32 *idx, size_t n_scalars, size_t n) {
     size_t jb = lcbk_ecdh_job_bytes() * n, pb = lcbk_ecdh_point_bytes() * n;
     void *jobs = c->ecies[W_JOBS].get(jb), *pts = c->ecies[W_PTS].get(pb);
-    if (!jobs || !pts) { set_error("device allocation failed"); return -1; }
+    if (!jobs || !pts) { set_err("device allocation failed"); return -1; }
     (void)hipEventRecord(c->ecies_ev[0], s);
     lcbk_ecdh_scalars(s, pub, off, min_len, scalars32, idx, (u32)(n_scalars > 0xffffffffu ? 0xffffffffu : n_scalars),
                       (u32)n, jobs);
@@ -67,7 +67,7 @@ int ecdh_core(lcb_ctx *c, hipStream_t s, uint8_t *key32, uint8_t *ok, const uint
 int ecdh_dev(lcb_ctx *c, hipStream_t s, uint8_t *key32, uint8_t *ok, const uint8_t *pub33, const uint8_t *scalars32,
              const u32 *idx, size_t n_scalars, size_t n) {
     if (!n) return 0;
-    if (!key32 || !ok || !pub33 || !scalars32) { set_error("secp ecdh: null pointer"); return -1; }
+    if (!key32 || !ok || !pub33 || !scalars32) { set_err("secp ecdh: null pointer"); return -1; }
     if (!size_ok("secp ecdh: batch too large", n) || !events_ready(c)) return -1;
     if (ecdh_core(c, s, key32, ok, pub33, nullptr, 0, scalars32, idx, idx ? n_scalars : n, n)) return -1;
     mark(c, s, 4);
@@ -76,7 +76,7 @@ int ecdh_dev(lcb_ctx *c, hipStream_t s, uint8_t *key32, uint8_t *ok, const uint8
 int gcm_encrypt_dev(lcb_ctx *c, hipStream_t s, uint8_t *out, const uint8_t *keys32, const uint8_t *nonces16,
                     const uint8_t *pt, const uint64_t *pt_off, size_t n) {
     if (!n) return 0;
-    if (!out || !keys32 || !nonces16 || !pt || !pt_off) { set_error("aes-256-gcm encrypt: null pointer"); return -1; }
+    if (!out || !keys32 || !nonces16 || !pt || !pt_off) { set_err("aes-256-gcm encrypt: null pointer"); return -1; }
     if (!size_ok("aes-256-gcm encrypt: batch too large", n) || !events_ready(c)) return -1;
     mark(c, s, 0);
     lcbk_gcm_encrypt(s, keys32, nonces16, pt, pt_off, (u32)n, out, nullptr, nullptr);
@@ -86,10 +86,10 @@ int gcm_encrypt_dev(lcb_ctx *c, hipStream_t s, uint8_t *out, const uint8_t *keys
 int gcm_decrypt_dev(lcb_ctx *c, hipStream_t s, uint8_t *pt_out, uint8_t *ok, const uint8_t *keys32, const uint8_t *ct,
                     const uint64_t *ct_off, size_t n) {
     if (!n) return 0;
-    if (!pt_out || !ok || !keys32 || !ct || !ct_off) { set_error("aes-256-gcm decrypt: null pointer"); return -1; }
+    if (!pt_out || !ok || !keys32 || !ct || !ct_off) { set_err("aes-256-gcm decrypt: null pointer"); return -1; }
     if (!size_ok("aes-256-gcm decrypt: batch too large", n) || !events_ready(c)) return -1;
     uint64_t *oo = (uint64_t *)c->ecies[W_OFF].get(8 * (n + 1));
-    if (!oo) { set_error("device allocation failed"); return -1; }
+    if (!oo) { set_err("device allocation failed"); return -1; }
     mark(c, s, 0);
     lcbk_gcm_offsets(s, ct_off, (u32)n, 32, oo);
     lcbk_gcm_decrypt(s, keys32, ct, ct_off, oo, (u32)n, 0, pt_out, ok, nullptr);
@@ -101,13 +101,13 @@ int envelope_encrypt_dev(lcb_ctx *c, hipStream_t s, uint8_t *out, uint8_t *ok, c
                          size_t n) {
     if (!n) return 0;
     if (!out || !ok || !recipient_pub33 || !eph_priv32 || !nonces16 || !pt || !pt_off) {
-        set_error("secp256k1 encrypt: null pointer");
+        set_err("secp256k1 encrypt: null pointer");
         return -1;
     }
     if (!size_ok("secp256k1 encrypt: batch too large", n) || !events_ready(c)) return -1;
     uint8_t *keys = (uint8_t *)c->ecies[W_KEYS].get(32 * n), *eok = (uint8_t *)c->ecies[W_EOK].get(n);
     uint8_t *eph = (uint8_t *)c->ecies[W_EPH].get(33 * n), *pok = (uint8_t *)c->ecies[W_POK].get(n);
-    if (!keys || !eok || !eph || !pok) { set_error("device allocation failed"); return -1; }
+    if (!keys || !eok || !eph || !pok) { set_err("device allocation failed"); return -1; }
     if (ecdh_core(c, s, keys, eok, recipient_pub33, nullptr, 0, eph_priv32, nullptr, n, n)) return -1;
     // the ephemeral public keys d G from the generator's comb table (timed with the GCM phase)
     if (lcb_ctx_ecdsa_pubkey_dev(c, eph, pok, eph_priv32, n, s)) { wipe(c->ecies[W_KEYS], 32 * n, s); return -1; }
@@ -121,11 +121,11 @@ int envelope_encrypt_dev(lcb_ctx *c, hipStream_t s, uint8_t *out, uint8_t *ok, c
 int envelope_decrypt_dev(lcb_ctx *c, hipStream_t s, uint8_t *pt_out, uint8_t *ok, const uint8_t *privs32,
                          const u32 *priv_idx, size_t n_privs, const uint8_t *ct, const uint64_t *ct_off, size_t n) {
     if (!n) return 0;
-    if (!pt_out || !ok || !privs32 || !ct || !ct_off) { set_error("secp256k1 decrypt: null pointer"); return -1; }
+    if (!pt_out || !ok || !privs32 || !ct || !ct_off) { set_err("secp256k1 decrypt: null pointer"); return -1; }
     if (!size_ok("secp256k1 decrypt: batch too large", n) || !events_ready(c)) return -1;
     uint8_t *keys = (uint8_t *)c->ecies[W_KEYS].get(32 * n), *eok = (uint8_t *)c->ecies[W_EOK].get(n);
     uint64_t *oo = (uint64_t *)c->ecies[W_OFF].get(8 * (n + 1));
-    if (!keys || !eok || !oo) { set_error("device allocation failed"); return -1; }
+    if (!keys || !eok || !oo) { set_err("device allocation failed"); return -1; }
     if (ecdh_core(c, s, keys, eok, ct, ct_off, 65, privs32, priv_idx, priv_idx ? n_privs : n, n)) return -1;
     lcbk_gcm_offsets(s, ct_off, (u32)n, 65, oo);
     lcbk_gcm_decrypt(s, keys, ct, ct_off, oo, (u32)n, 33, pt_out, ok, eok);
@@ -139,7 +139,7 @@ int envelope_decrypt_dev(lcb_ctx *c, hipStream_t s, uint8_t *pt_out, uint8_t *ok
 bool host_offsets(const char *what, std::vector<uint64_t> &rel, const uint64_t *off, size_t n) {
     rel.resize(n + 1);
     for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) { set_error(what); return false; }
+        if (off[i + 1] < off[i]) { set_err(what); return false; }
     for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
     return true;
 }
@@ -233,11 +233,11 @@ extern "C" int lcb_ctx_ecies_phase_ms(lcb_ctx *ctx, float ms[4]) {
     lcb_ctx *c = ctx_resolve(ctx);
     if (!c) return -1;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (!c->ecies_ran) { set_error("no ECIES call has run in this context"); return -1; }
+    if (!c->ecies_ran) { set_err("no ECIES call has run in this context"); return -1; }
     for (int k = 0; k < 4; k++) {
         hipError_t e = hipEventSynchronize(c->ecies_ev[k + 1]);
         if (e == hipSuccess) e = hipEventElapsedTime(&ms[k], c->ecies_ev[k], c->ecies_ev[k + 1]);
-        if (e != hipSuccess) { set_error("ecies phase timing", e); return -1; }
+        if (e != hipSuccess) { set_err("ecies phase timing", e); return -1; }
     }
     return 0;
 }
@@ -249,7 +249,7 @@ extern "C" int lcb_secp_ecdh_batch(uint8_t *key32_out, uint8_t *ok, const uint8_
     lcb_ctx *c = ctx_sync();
     if (!c) return -1;
     if (!n) return 0;
-    if (!key32_out || !ok || !pub33 || !scalars32) { set_error("secp ecdh: null pointer"); return -1; }
+    if (!key32_out || !ok || !pub33 || !scalars32) { set_err("secp ecdh: null pointer"); return -1; }
     if (!size_ok("secp ecdh: batch too large", n)) return -1;
     Enq q(c, c->stream);
     hipStream_t s = c->stream;
@@ -258,7 +258,7 @@ extern "C" int lcb_secp_ecdh_batch(uint8_t *key32_out, uint8_t *ok, const uint8_
     u32 *didx = scalar_idx ? (u32 *)stage(c, S_IDX, scalar_idx, 4 * n, s) : nullptr;
     uint8_t *dout = (uint8_t *)c->ecies[S_OUT].get(33 * n);
     int rc = -1;
-    if (!dpub || !dsc || (scalar_idx && !didx) || !dout) set_error("device allocation failed");
+    if (!dpub || !dsc || (scalar_idx && !didx) || !dout) set_err("device allocation failed");
     else rc = ecdh_dev(c, s, dout, dout + 32 * n, dpub, dsc, didx, ns, n);
     if (!rc) {
         hipMemcpyAsync(key32_out, dout, 32 * n, hipMemcpyDeviceToHost, s);
@@ -266,14 +266,14 @@ extern "C" int lcb_secp_ecdh_batch(uint8_t *key32_out, uint8_t *ok, const uint8_
     }
     wipe(c->ecies[S_SCALAR], 32 * ns, s);
     wipe(c->ecies[S_OUT], 33 * n, s);
-    return sync_ok(c, "secp ecdh") && !rc ? 0 : -1;
+    return sync_check(c, "secp ecdh") && !rc ? 0 : -1;
 }
 extern "C" int lcb_aes256_gcm_encrypt_batch(uint8_t *out, const uint8_t *keys32, const uint8_t *nonces16,
                                             const uint8_t *pt, const uint64_t *pt_off, size_t n) {
     lcb_ctx *c = ctx_sync();
     if (!c) return -1;
     if (!n) return 0;
-    if (!out || !keys32 || !nonces16 || !pt || !pt_off) { set_error("aes-256-gcm encrypt: null pointer"); return -1; }
+    if (!out || !keys32 || !nonces16 || !pt || !pt_off) { set_err("aes-256-gcm encrypt: null pointer"); return -1; }
     if (!size_ok("aes-256-gcm encrypt: batch too large", n)) return -1;
     std::vector<uint64_t> rel;
     if (!host_offsets("aes-256-gcm encrypt: offsets must not decrease", rel, pt_off, n)) return -1;
@@ -285,18 +285,18 @@ extern "C" int lcb_aes256_gcm_encrypt_batch(uint8_t *out, const uint8_t *keys32,
     uint64_t *doff = (uint64_t *)stage(c, S_IDX, rel.data(), 8 * (n + 1), s);
     uint8_t *dout = (uint8_t *)c->ecies[S_OUT].get(ob);
     int rc = -1;
-    if (!dk || !dn || !dd || !doff || !dout) set_error("device allocation failed");
+    if (!dk || !dn || !dd || !doff || !dout) set_err("device allocation failed");
     else rc = gcm_encrypt_dev(c, s, dout, dk, dn, dd, doff, n);
     if (!rc) hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, s);
     wipe(c->ecies[S_KEYS], 32 * n, s);
-    return sync_ok(c, "aes-256-gcm encrypt") && !rc ? 0 : -1;
+    return sync_check(c, "aes-256-gcm encrypt") && !rc ? 0 : -1;
 }
 extern "C" int lcb_aes256_gcm_decrypt_batch(uint8_t *pt_out, uint8_t *ok, const uint8_t *keys32, const uint8_t *ct,
                                             const uint64_t *ct_off, size_t n) {
     lcb_ctx *c = ctx_sync();
     if (!c) return -1;
     if (!n) return 0;
-    if (!pt_out || !ok || !keys32 || !ct || !ct_off) { set_error("aes-256-gcm decrypt: null pointer"); return -1; }
+    if (!pt_out || !ok || !keys32 || !ct || !ct_off) { set_err("aes-256-gcm decrypt: null pointer"); return -1; }
     if (!size_ok("aes-256-gcm decrypt: batch too large", n)) return -1;
     std::vector<uint64_t> rel;
     if (!host_offsets("aes-256-gcm decrypt: offsets must not decrease", rel, ct_off, n)) return -1;
@@ -307,14 +307,14 @@ extern "C" int lcb_aes256_gcm_decrypt_batch(uint8_t *pt_out, uint8_t *ok, const 
     uint64_t *doff = (uint64_t *)stage(c, S_IDX, rel.data(), 8 * (n + 1), s);
     uint8_t *dout = (uint8_t *)c->ecies[S_OUT].get(pb + n);
     int rc = -1;
-    if (!dk || !dd || !doff || !dout) set_error("device allocation failed");
+    if (!dk || !dd || !doff || !dout) set_err("device allocation failed");
     else rc = gcm_decrypt_dev(c, s, dout, dout + pb, dk, dd, doff, n);
     if (!rc) {
         if (pb) hipMemcpyAsync(pt_out, dout, pb, hipMemcpyDeviceToHost, s);
         hipMemcpyAsync(ok, dout + pb, n, hipMemcpyDeviceToHost, s);
     }
     wipe(c->ecies[S_KEYS], 32 * n, s);
-    return sync_ok(c, "aes-256-gcm decrypt") && !rc ? 0 : -1;
+    return sync_check(c, "aes-256-gcm decrypt") && !rc ? 0 : -1;
 }
 extern "C" int lcb_secp256k1_encrypt_batch(uint8_t *out, uint8_t *ok, const uint8_t *recipient_pub33,
                                            const uint8_t *eph_priv32, const uint8_t *nonces16, const uint8_t *pt,
@@ -323,7 +323,7 @@ extern "C" int lcb_secp256k1_encrypt_batch(uint8_t *out, uint8_t *ok, const uint
     if (!c) return -1;
     if (!n) return 0;
     if (!out || !ok || !recipient_pub33 || !eph_priv32 || !nonces16 || !pt || !pt_off) {
-        set_error("secp256k1 encrypt: null pointer");
+        set_err("secp256k1 encrypt: null pointer");
         return -1;
     }
     if (!size_ok("secp256k1 encrypt: batch too large", n)) return -1;
@@ -338,21 +338,21 @@ extern "C" int lcb_secp256k1_encrypt_batch(uint8_t *out, uint8_t *ok, const uint
     uint64_t *doff = (uint64_t *)stage(c, S_IDX, rel.data(), 8 * (n + 1), s);
     uint8_t *dout = (uint8_t *)c->ecies[S_OUT].get(ob + n);
     int rc = -1;
-    if (!dpub || !dsc || !dn || !dd || !doff || !dout) set_error("device allocation failed");
+    if (!dpub || !dsc || !dn || !dd || !doff || !dout) set_err("device allocation failed");
     else rc = envelope_encrypt_dev(c, s, dout, dout + ob, dpub, dsc, dn, dd, doff, n);
     if (!rc) {
         hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, s);
         hipMemcpyAsync(ok, dout + ob, n, hipMemcpyDeviceToHost, s);
     }
     wipe(c->ecies[S_SCALAR], 32 * n, s);
-    return sync_ok(c, "secp256k1 encrypt") && !rc ? 0 : -1;
+    return sync_check(c, "secp256k1 encrypt") && !rc ? 0 : -1;
 }
 extern "C" int lcb_secp256k1_decrypt_batch(uint8_t *pt_out, uint8_t *ok, const uint8_t *privs32, const uint32_t *priv_idx,
                                            size_t n_privs, const uint8_t *ct, const uint64_t *ct_off, size_t n) {
     lcb_ctx *c = ctx_sync();
     if (!c) return -1;
     if (!n) return 0;
-    if (!pt_out || !ok || !privs32 || !ct || !ct_off) { set_error("secp256k1 decrypt: null pointer"); return -1; }
+    if (!pt_out || !ok || !privs32 || !ct || !ct_off) { set_err("secp256k1 decrypt: null pointer"); return -1; }
     if (!size_ok("secp256k1 decrypt: batch too large", n)) return -1;
     std::vector<uint64_t> rel;
     if (!host_offsets("secp256k1 decrypt: offsets must not decrease", rel, ct_off, n)) return -1;
@@ -364,12 +364,12 @@ extern "C" int lcb_secp256k1_decrypt_batch(uint8_t *pt_out, uint8_t *ok, const u
     uint64_t *doff = (uint64_t *)stage(c, S_IDX, rel.data(), 8 * (n + 1), s);
     uint8_t *dout = (uint8_t *)c->ecies[S_OUT].get(pb + n);
     int rc = -1;
-    if (!dsc || !dd || (priv_idx && !didx) || !doff || !dout) set_error("device allocation failed");
+    if (!dsc || !dd || (priv_idx && !didx) || !doff || !dout) set_err("device allocation failed");
     else rc = envelope_decrypt_dev(c, s, dout, dout + pb, dsc, didx, np, dd, doff, n);
     if (!rc) {
         if (pb) hipMemcpyAsync(pt_out, dout, pb, hipMemcpyDeviceToHost, s);
         hipMemcpyAsync(ok, dout + pb, n, hipMemcpyDeviceToHost, s);
     }
     wipe(c->ecies[S_SCALAR], 32 * np, s);
-    return sync_ok(c, "secp256k1 decrypt") && !rc ? 0 : -1;
+    return sync_check(c, "secp256k1 decrypt") && !rc ? 0 : -1;
 }

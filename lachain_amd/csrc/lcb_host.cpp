@@ -1,19 +1,16 @@
-// lachain_amd/csrc/lcb_host.cpp — host implementation of include/lachain_bls.h (liblachain_bls.so).
+// lachain_amd/csrc/lcb_host.cpp — the core of liblachain_bls.so's host side (include/lachain_bls.h): device
+// initialisation and configuration, the scratch gate, the execution contexts, and the exact batch paths on them —
+// TPKE and threshold-signature preparation / verification / combination, the coin folds, batch Lagrange, scalar
+// multiplication, hashing to G2, the Pippenger MSM and the KDF — with their debug and tuning hooks.
 //
-// Batch work (share verification, Lagrange combination, MSM, scalar multiplications, pairings, hashing to G2) runs
-// on gfx950 kernels (k_*.hip).  The mcl single-element calls that are O(1) field work — Fr arithmetic (fr_host.hpp)
-// and G1 / G2 add, sub, neg, dbl, normalize, compare, validity, (de)serialization, GT products (fp_host.hpp) — run on
-// the calling thread, word for word the kernels' formulas, because a GPU round trip costs 50-100x the operation.
+// Elsewhere: the mcl single-element surface (lcb_mcl.cpp), the randomized batch check behind the *_batched entry
+// points (lcb_batch.cpp; the exact checks and the preparations both use are here), the trustless-DKG commitments
+// (lcb_dkg.cpp), Reed-Solomon and the reliable-broadcast Merkle layer (lcb_rbc.cpp), secp256k1 ECDSA / ECIES
+// (lcb_ecdsa.cpp, lcb_ecies.cpp) and transaction hashing (lcb_txhash.cpp).  What they share is in lcb_internal.hpp.
 // There is deliberately no CPU fallback for the GPU work: without a gfx950 device mclBn_init returns -1 and every
 // entry point fails (returns -1 / 0 bytes / leaves outputs zeroed) with lcb_last_error() describing why.
-// The randomized batch check (the *_batched entry points' driver) is lcb_batch.cpp; the exact checks and the
-// preparations both use are here.
 //
-// Concurrency model (the reference calls mcl from one thread per consensus protocol,
-// /root/reference/src/Lachain.Consensus/AbstractProtocol.cs:46-47):
-//   * scalar Fr arithmetic runs on the host (fr_host.hpp); every other single-element mcl operation is a GPU round trip
-//     on the calling thread's own staging buffers and stream (no process-wide lock), and the pairing, multi-scalar
-//     products, Lagrange interpolation and polynomial evaluation go to batch / cooperative kernels;
+// Concurrency model of the batch entry points (the single-element calls' is in lcb_mcl.cpp):
 //   * every batch entry point runs in an lcb_ctx — explicit (lcb_ctx_*) or the calling thread's own default
 //     context — which owns all device workspaces the call needs (TPKE and TS line sets separately, Lagrange,
 //     MSM, staging).  A context's work executes in the order it was enqueued whatever stream it is enqueued on
@@ -29,7 +26,6 @@
 #include <vector>
 #include <string>
 #include <algorithm>
-#include <sys/random.h>
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
 
@@ -39,70 +35,49 @@
 #include "host_sha3.hpp"
 #include "lcb_ctx.hpp"
 #include "lcb_internal.hpp"
-#include "fr_host.hpp"
 #include "fp_host.hpp"
 
 using namespace lcb_int;
 
 namespace {
-
 std::mutex g_mu;               // device initialisation
 int g_device = 0;
 bool g_ready = false;
-int g_orig_cofactor = 0;
-const size_t IO_WORDS = 4096; // 16 KB staging per thread
 thread_local std::string g_err;
 thread_local uint64_t g_err_count = 0;   // failures on this thread (lcb_error_count): the void mcl entry points have no
                                          // return code, so a caller detects their failure by this counter changing
 thread_local int t_bound_device = -1;
+std::atomic<int> g_inject_site{0}, g_inject_count{0};   // lcb_test_inject_failure
+} // namespace
+int lcb_int::g_orig_cofactor = 0;
 
-void set_err(const char *what, hipError_t e = hipSuccess) {
+void lcb_int::set_err(const char *what, hipError_t e) {
     char buf[256];
     if (e != hipSuccess) snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
     else snprintf(buf, sizeof buf, "%s", what);
     g_err = buf;
     g_err_count++;
 }
-
-// fault injection (lcb_test_inject_failure, LCB_ALLOW_TEST_HOOKS=1): the next `count` passes through site `site` fail
-std::atomic<int> g_inject_site{0}, g_inject_count{0};
-bool injected(int site) {
+bool lcb_int::injected(int site) {
     if (g_inject_site.load(std::memory_order_relaxed) != site) return false;
     int c = g_inject_count.load();
     while (c > 0)
         if (g_inject_count.compare_exchange_weak(c, c - 1)) return true;
     return false;
 }
-enum { INJ_STAGE_HOST_ALLOC = 1, INJ_CT_CACHE_ALLOC = 2, INJ_PAIRING_ALLOC = 3, INJ_STAGE_OP = 4 };
-bool inject_armed(int site) {             // a pending failure at `site` (not consumed)
+bool lcb_int::inject_armed(int site) {
     return g_inject_site.load(std::memory_order_relaxed) == site && g_inject_count.load() > 0;
 }
 
-// the output of a failed void mcl call (mclBnG1_mul, mclBn_pairing, ...): random words with the top limb of the first
-// coordinate set to all ones, so it is not a canonical field element (isValid / serialize reject it), and two failed
-// calls never compare equal (an equality check between two failed pairings cannot pass)
-void fail_out(void *out, size_t bytes) {
-    uint8_t *b = (uint8_t *)out;
-    size_t got = 0;
-    while (got < bytes) {
-        ssize_t r = getrandom(b + got, bytes - got, 0);
-        if (r <= 0) break;
-        got += (size_t)r;
-    }
-    for (size_t i = got; i < bytes; i++) b[i] = (uint8_t)(0x5a ^ i);
-    if (bytes >= 48) memset(b + 44, 0xff, 4);
-}
-
 // HIP's current device is per thread: bind every thread that enters the library to the configured device
-bool bind_thread() {
+static bool bind_thread() {
     if (t_bound_device == g_device) return true;
     hipError_t e = hipSetDevice(g_device);
     if (e != hipSuccess) { set_err("hipSetDevice", e); return false; }
     t_bound_device = g_device;
     return true;
 }
-
-bool init_locked() {
+static bool init_locked() {
     if (g_ready) return bind_thread();
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
@@ -114,112 +89,12 @@ bool init_locked() {
     g_ready = true;
     return true;
 }
-
-// the library is usable from this thread (device opened once per process, bound once per thread)
-bool ready() {
+bool lcb_int::ready() {
     if (g_ready && t_bound_device == g_device) return true;
     std::lock_guard<std::mutex> lk(g_mu);
     return init_locked();
 }
-
-// single-element operations: every calling thread owns its staging (device and pinned host buffers, a stream), so the
-// protocol threads (AbstractProtocol.cs:46-47) never queue behind each other's round trips
-// A thread's staging and implicit contexts are NOT released when it exits: HIP calls from thread-local destructors
-// race the runtime's (and a profiler's) own per-thread teardown (an abort under rocprofv3 in round 4).  They are
-// retired to process-wide free lists instead and handed to the next thread that needs one, so their number stays
-// bounded by the peak number of calling threads.  The lists are leaked on purpose (no static-destruction order issue).
-struct StageRes {
-    u32 *dev = nullptr, *host = nullptr;
-    hipStream_t s = nullptr;
-};
-std::mutex &retired_mu() {
-    static std::mutex *m = new std::mutex;
-    return *m;
-}
-std::vector<StageRes> &retired_stages() {
-    static std::vector<StageRes> *v = new std::vector<StageRes>;
-    return *v;
-}
-struct OpStage : StageRes {
-    ~OpStage() {
-        if (!(s && dev && host)) return;             // a half-built stage never survives stage_ready
-        std::lock_guard<std::mutex> lk(retired_mu());
-        retired_stages().push_back(*this);
-    }
-};
-thread_local OpStage t_stage;
-bool stage_ready() {
-    if (!ready()) return false;
-    if (t_stage.s && t_stage.dev && t_stage.host) return true;
-    {
-        std::lock_guard<std::mutex> lk(retired_mu());
-        auto &v = retired_stages();
-        // (a pending staging-allocation failure builds a new stage, so the test hook reaches the allocation)
-        if (!v.empty() && !t_stage.s && !t_stage.dev && !t_stage.host && !inject_armed(INJ_STAGE_HOST_ALLOC)) {
-            static_cast<StageRes &>(t_stage) = v.back();
-            v.pop_back();
-            return true;
-        }
-    }
-    // all three or none: a partial failure releases what was created, so the next call retries from scratch instead
-    // of passing a half-built stage (a set stream with a null host buffer would be written through)
-    hipError_t e = t_stage.s ? hipSuccess : hipStreamCreateWithFlags(&t_stage.s, hipStreamNonBlocking);
-    if (e == hipSuccess && !t_stage.dev) e = hipMalloc(&t_stage.dev, IO_WORDS * 4);
-    if (e == hipSuccess && !t_stage.host) {
-        if (injected(INJ_STAGE_HOST_ALLOC)) e = hipErrorOutOfMemory;
-        else e = hipHostMalloc(&t_stage.host, IO_WORDS * 4, hipHostMallocDefault);
-    }
-    if (e != hipSuccess) {
-        set_err("single-operation staging", e);
-        if (t_stage.host) (void)hipHostFree(t_stage.host);
-        if (t_stage.dev) (void)hipFree(t_stage.dev);
-        if (t_stage.s) (void)hipStreamDestroy(t_stage.s);
-        t_stage.host = nullptr;
-        t_stage.dev = nullptr;
-        t_stage.s = nullptr;
-        return false;
-    }
-    return true;
-}
-#define IOH (t_stage.host)
-
-// run one k_op on the thread's staging buffer: copy `in_words` words to the device, launch, copy `out_words` back
-bool run_op(int op, size_t in_words, size_t out_words) {
-    hipError_t e;
-    if (injected(INJ_STAGE_OP)) { set_err("injected failure (single operation)"); return false; }
-    if ((e = hipMemcpyAsync(t_stage.dev, t_stage.host, in_words * 4, hipMemcpyHostToDevice, t_stage.s)) != hipSuccess) { set_err("H2D", e); return false; }
-    lcbk_op(dim3(1), t_stage.s, op, t_stage.dev, g_orig_cofactor);
-    if ((e = hipGetLastError()) != hipSuccess) { set_err("k_op launch", e); return false; }
-    if ((e = hipMemcpyAsync(t_stage.host, t_stage.dev, out_words * 4, hipMemcpyDeviceToHost, t_stage.s)) != hipSuccess) { set_err("D2H", e); return false; }
-    if ((e = hipStreamSynchronize(t_stage.s)) != hipSuccess) { set_err("k_op", e); return false; }
-    return true;
-}
-
-// mclBnG2_hashAndMapTo's round trip: as run_op, on the dedicated one-lane hash kernel (k_ptmul.hip)
-bool run_hash(size_t in_words, size_t out_words) {
-    hipError_t e;
-    if (injected(INJ_STAGE_OP)) { set_err("injected failure (single operation)"); return false; }
-    if ((e = hipMemcpyAsync(t_stage.dev, t_stage.host, in_words * 4, hipMemcpyHostToDevice, t_stage.s)) != hipSuccess) { set_err("H2D", e); return false; }
-    lcbk_mcl_g2_hash(t_stage.s, t_stage.dev, g_orig_cofactor);
-    if ((e = hipGetLastError()) != hipSuccess) { set_err("k_mcl_g2_hash launch", e); return false; }
-    if ((e = hipMemcpyAsync(t_stage.host, t_stage.dev, out_words * 4, hipMemcpyDeviceToHost, t_stage.s)) != hipSuccess) { set_err("D2H", e); return false; }
-    if ((e = hipStreamSynchronize(t_stage.s)) != hipSuccess) { set_err("k_mcl_g2_hash", e); return false; }
-    return true;
-}
-
-#define LOCKED_OR(ret)                        \
-    if (!stage_ready()) return ret;
-
-// canonical Fr bytes (32-byte LE < r)
-bool fr_bytes_lt_r(const uint8_t *b) {
-    for (int j = 7; j >= 0; j--) {
-        uint32_t w = (uint32_t)b[4 * j] | (uint32_t)b[4 * j + 1] << 8 | (uint32_t)b[4 * j + 2] << 16 | (uint32_t)b[4 * j + 3] << 24;
-        if (w != LCB_R_HOST[j]) return w < LCB_R_HOST[j];
-    }
-    return false;
-}
-
-} // namespace
+int lcb_int::device() { return g_device; }
 
 // opt-in switches read from the environment at call time: the tuning hooks (lcb_set_coop_max, ...) change the kernel
 // families a batch runs on and the fault-injection hooks make calls fail; neither belongs in a production process
@@ -425,522 +300,6 @@ extern "C" void lcb_scratch_gate_stats(uint64_t *routed, uint64_t *seen) {
     if (seen) *seen = g_gate_seen.load();
 }
 
-extern "C" int mclBn_init(int curve, int compiledTimeVar) {
-    if (curve != MCL_BLS12_381 || compiledTimeVar != MCLBN_COMPILED_TIME_VAR) {
-        set_err("unsupported curve / compiledTimeVar");
-        return -1;
-    }
-    std::lock_guard<std::mutex> lk(g_mu);
-    return init_locked() ? 0 : -1;
-}
-extern "C" int mclBn_getOpUnitSize(void) { return 6; }
-extern "C" int mclBn_getG1ByteSize(void) { return 48; }
-extern "C" int mclBn_getFrByteSize(void) { return 32; }
-extern "C" int mclBn_getFpByteSize(void) { return 48; }
-
-// ================================================================== Fr (host arithmetic, fr_host.hpp)
-static inline const uint64_t *FRV(const mclBnFr *x) { return (const uint64_t *)x; }
-static inline uint64_t *FRW(mclBnFr *x) { return (uint64_t *)x; }
-static int fr_set_raw(mclBnFr *y, const u32 raw[8]) {
-    uint64_t r[4];
-    memcpy(r, raw, 32);
-    if (!frh::lt_r(r)) { memset(y, 0, 32); return -1; }
-    frh::from_raw(FRW(y), r);
-    return 0;
-}
-static int fr_get_raw(u32 raw[8], const mclBnFr *x) {
-    uint64_t r[4];
-    frh::to_raw(r, FRV(x));
-    memcpy(raw, r, 32);
-    return 0;
-}
-extern "C" int mclBnFr_setInt(mclBnFr *y, mclInt x) {
-    u32 raw[8] = {0};
-    uint64_t ax = x < 0 ? (uint64_t)(-(x + 1)) + 1 : (uint64_t)x;
-    raw[0] = (u32)ax; raw[1] = (u32)(ax >> 32);
-    if (fr_set_raw(y, raw)) return -1;
-    if (x < 0) mclBnFr_neg(y, y);
-    return 0;
-}
-extern "C" int mclBnFr_setInt32(mclBnFr *y, int x) { return mclBnFr_setInt(y, x); }
-extern "C" int mclBnFr_setByCSPRNG(mclBnFr *x) {
-    // rejection sampling of a uniform 255-bit value < r
-    for (int tries = 0; tries < 64; tries++) {
-        u32 raw[8];
-        if (getrandom(raw, sizeof raw, 0) != (ssize_t)sizeof raw) return -1;
-        raw[7] &= 0x7fffffffu;
-        if (fr_set_raw(x, raw) == 0) return 0;
-    }
-    return -1;
-}
-extern "C" int mclBnFr_setLittleEndian(mclBnFr *x, const void *buf, mclSize n) {
-    // mcl setArrayMask: take at most 32 bytes, mask to 255 bits, and to 254 if still >= r
-    u32 raw[8] = {0};
-    memcpy(raw, buf, n < 32 ? n : 32);
-    raw[7] &= 0x7fffffffu;
-    uint64_t r[4];
-    memcpy(r, raw, 32);
-    if (!frh::lt_r(r)) raw[7] &= 0x3fffffffu;
-    return fr_set_raw(x, raw);
-}
-extern "C" mclSize mclBnFr_serialize(void *buf, mclSize max, const mclBnFr *x) {
-    if (max < 32) return 0;
-    u32 raw[8];
-    fr_get_raw(raw, x);
-    memcpy(buf, raw, 32);
-    return 32;
-}
-extern "C" mclSize mclBnFr_deserialize(mclBnFr *x, const void *buf, mclSize n) {
-    if (n < 32) return 0;
-    u32 raw[8];
-    memcpy(raw, buf, 32);
-    return fr_set_raw(x, raw) == 0 ? 32 : 0;
-}
-extern "C" void mclBnFr_clear(mclBnFr *x) { memset(x, 0, sizeof *x); }
-extern "C" int mclBnFr_isValid(const mclBnFr *x) { return frh::lt_r(FRV(x)); }
-extern "C" int mclBnFr_isEqual(const mclBnFr *x, const mclBnFr *y) { return memcmp(x, y, 32) == 0; }
-extern "C" int mclBnFr_isZero(const mclBnFr *x) { return frh::is_zero(FRV(x)); }
-extern "C" int mclBnFr_isOne(const mclBnFr *x) { return memcmp(x, frh::ONE, 32) == 0; }
-extern "C" void mclBnFr_neg(mclBnFr *y, const mclBnFr *x) { frh::neg(FRW(y), FRV(x)); }
-extern "C" void mclBnFr_inv(mclBnFr *y, const mclBnFr *x) { frh::inv(FRW(y), FRV(x)); }
-extern "C" void mclBnFr_sqr(mclBnFr *y, const mclBnFr *x) { frh::mul(FRW(y), FRV(x), FRV(x)); }
-extern "C" void mclBnFr_add(mclBnFr *z, const mclBnFr *x, const mclBnFr *y) { frh::add(FRW(z), FRV(x), FRV(y)); }
-extern "C" void mclBnFr_sub(mclBnFr *z, const mclBnFr *x, const mclBnFr *y) { frh::sub(FRW(z), FRV(x), FRV(y)); }
-extern "C" void mclBnFr_mul(mclBnFr *z, const mclBnFr *x, const mclBnFr *y) { frh::mul(FRW(z), FRV(x), FRV(y)); }
-extern "C" void mclBnFr_div(mclBnFr *z, const mclBnFr *x, const mclBnFr *y) {
-    mclBnFr t;
-    mclBnFr_inv(&t, y);
-    mclBnFr_mul(z, x, &t);
-}
-
-// ================================================================== G1 / G2 (host field work, fp_host.hpp)
-// O(1) field work runs on the host like Fr (fp_host.hpp header); G1 / G2 multiplication, the hash to G2 and the
-// pairing below stay on the GPU.  Bit-identical to the kernels' results (same formulas, fully reduced residues).
-static void g1_op(int op, mclBnG1 *z, const mclBnG1 *x, const mclBnG1 *y, const mclBnFr *k) {
-    if (!stage_ready()) { fail_out(z, 144); return; }
-    memcpy(IOH + 36, x, 144);
-    if (y) memcpy(IOH + 72, y, 144);
-    if (k) memcpy(IOH + 108, k, 32);
-    if (run_op(op, 116, 36)) memcpy(z, IOH, 144);
-    else fail_out(z, 144);
-}
-std::atomic<int> g_g2_sign_b{0};      // lcb_set_g2_sign_from_b: the G2 wire flag is parity(y.b) instead of parity(y.a)
-static inline fph::g1 *G1W(mclBnG1 *x) { return (fph::g1 *)x; }
-static inline const fph::g1 *G1R(const mclBnG1 *x) { return (const fph::g1 *)x; }
-static inline fph::g2 *G2W(mclBnG2 *x) { return (fph::g2 *)x; }
-static inline const fph::g2 *G2R(const mclBnG2 *x) { return (const fph::g2 *)x; }
-extern "C" mclSize mclBnG1_serialize(void *buf, mclSize max, const mclBnG1 *x) {
-    if (max < 48) return 0;
-    fph::g1_compress((uint8_t *)buf, *G1R(x));
-    return 48;
-}
-extern "C" mclSize mclBnG1_deserialize(mclBnG1 *x, const void *buf, mclSize n) {
-    if (n < 48) return 0;
-    fph::g1a a;
-    if (!fph::g1_decompress(a, (const uint8_t *)buf)) return 0;
-    fph::jac_from_aff(*G1W(x), a);
-    return 48;
-}
-extern "C" int mclBnG1_isValid(const mclBnG1 *x) { return fph::jac_valid(*G1R(x)); }
-extern "C" int mclBnG1_isEqual(const mclBnG1 *x, const mclBnG1 *y) { return fph::jac_eq(*G1R(x), *G1R(y)); }
-extern "C" int mclBnG1_isZero(const mclBnG1 *x) {
-    static const u32 z[12] = {0};
-    return memcmp(&x->z, z, 48) == 0;
-}
-extern "C" void mclBnG1_clear(mclBnG1 *x) { memset(x, 0, sizeof *x); }
-extern "C" void mclBnG1_neg(mclBnG1 *y, const mclBnG1 *x) { fph::jac_neg(*G1W(y), *G1R(x)); }
-extern "C" void mclBnG1_dbl(mclBnG1 *y, const mclBnG1 *x) { fph::g1 t; fph::jac_dbl(t, *G1R(x)); *G1W(y) = t; }
-extern "C" void mclBnG1_normalize(mclBnG1 *y, const mclBnG1 *x) { fph::jac_normalize(*G1W(y), *G1R(x)); }
-extern "C" void mclBnG1_add(mclBnG1 *z, const mclBnG1 *x, const mclBnG1 *y) {
-    fph::g1 t;
-    fph::jac_add(t, *G1R(x), *G1R(y));
-    *G1W(z) = t;
-}
-extern "C" void mclBnG1_sub(mclBnG1 *z, const mclBnG1 *x, const mclBnG1 *y) {
-    fph::g1 ny, t;
-    fph::jac_neg(ny, *G1R(y));
-    fph::jac_add(t, *G1R(x), ny);
-    *G1W(z) = t;
-}
-// ---- mclBnG1_mul / mclBnG2_mul: the cooperative ladders of k_ptmul.hip (four lanes per ladder, several ladders per
-// wave) on the scalar split below, the result assembled here; a base point outside the subgroup (the split is only
-// valid on it) takes the exact one-lane ladder of k_op
-struct PtJobG1 { u32 x[12], y[12], inf, nwin, pad[2]; uint8_t nib[36]; };
-struct PtJobG2 { u32 x[24], y[24], inf, nwin, pad[2]; uint8_t nib[36]; };
-static_assert(sizeof(PtJobG1) == 148 && sizeof(PtJobG2) == 244, "k_ptmul.hip PtJob layouts");
-typedef unsigned __int128 u128h;
-static const uint64_t Z_ABS_H = 0xd201000000010000ull;
-// q <- q / u (256-bit), returns q mod u
-static uint64_t divmod_u(uint64_t q[4]) {
-    u128h rem = 0;
-    for (int i = 3; i >= 0; i--) {
-        u128h cur = rem << 64 | q[i];
-        q[i] = (uint64_t)(cur / Z_ABS_H);
-        rem = cur % Z_ABS_H;
-    }
-    return (uint64_t)rem;
-}
-// nwin signed 4-bit digits of the little-endian words v (nw 64-bit words), most significant first: each window's
-// nibble plus the carry, minus 16 (carry 1) when above 8, so every digit is in [-7, 8] and k_ptmul.hip's table holds
-// T[1..8].  A byte is |digit| with bit 7 set for a negative digit.  False if a carry leaves the top window (the
-// callers size nwin so that it cannot: 33 windows for < 2^129, 17 for one 64-bit word).
-template <class J> static bool put_digits(J &job, const uint64_t *v, int nw, u32 nwin) {
-    job.nwin = nwin;
-    int carry = 0;
-    for (u32 i = 0; i < nwin; i++) {              // i: window index from the least significant
-        const u32 bit = 4 * i, word = bit / 64;
-        int d = (word < (u32)nw ? (int)((v[word] >> (bit % 64)) & 15) : 0) + carry;
-        carry = d > 8;
-        if (carry) d -= 16;
-        job.nib[nwin - 1 - i] = d < 0 ? (uint8_t)(0x80 | -d) : (uint8_t)d;
-    }
-    return carry == 0;
-}
-template <class J, class A> static void put_point(J &job, const A &a) {
-    job.inf = a.inf ? 1u : 0u;
-    memcpy(job.x, &a.x, sizeof a.x);
-    memcpy(job.y, &a.y, sizeof a.y);
-}
-// run n_jobs ladders (k_ptmul_g1 / _g2) on the thread's staging; outputs the groups' Jacobian results
-static bool ptmul_run(int g, const void *jobs, size_t job_bytes, u32 n_jobs, void *out, size_t out_bytes) {
-    if (!stage_ready()) return false;
-    if (injected(INJ_STAGE_OP)) { set_err("injected failure (single operation)"); return false; }
-    memcpy(IOH, jobs, job_bytes * n_jobs);
-    const size_t out_w = 1024;                    // results at word 1024 of the 16 KB staging
-    hipError_t e;
-    if ((e = hipMemcpyAsync(t_stage.dev, t_stage.host, job_bytes * n_jobs, hipMemcpyHostToDevice, t_stage.s)) != hipSuccess) { set_err("H2D", e); return false; }
-    if (g == 1) lcbk_ptmul_g1(t_stage.s, t_stage.dev, n_jobs, t_stage.dev + out_w);
-    else lcbk_ptmul_g2(t_stage.s, t_stage.dev, n_jobs, t_stage.dev + out_w);
-    if ((e = hipGetLastError()) != hipSuccess) { set_err("k_ptmul launch", e); return false; }
-    if ((e = hipMemcpyAsync(t_stage.host + out_w, t_stage.dev + out_w, out_bytes * n_jobs, hipMemcpyDeviceToHost, t_stage.s)) != hipSuccess) { set_err("D2H", e); return false; }
-    if ((e = hipStreamSynchronize(t_stage.s)) != hipSuccess) { set_err("k_ptmul", e); return false; }
-    memcpy(out, IOH + out_w, out_bytes * n_jobs);
-    return true;
-}
-extern "C" void mclBnG1_mul(mclBnG1 *z, const mclBnG1 *x, const mclBnFr *y) {
-    uint64_t k[4];
-    frh::to_raw(k, FRV(y));                       // canonical scalar < r
-    fph::g1a P;
-    fph::jac_to_aff(P, *G1R(x));
-    if (P.inf || (k[0] | k[1] | k[2] | k[3]) == 0 || !fph::jac_on_curve(*G1R(x))) {
-        if (P.inf || (k[0] | k[1] | k[2] | k[3]) == 0) { fph::jac_set_inf(*G1W(z)); return; }
-        g1_op(OP_G1_MUL, z, x, nullptr, y);       // not a curve point: mcl's generic ladder semantics
-        return;
-    }
-    // GLV (curve.hpp g1_mul_glv): k = d0 + d1 u + a1 u^2 = (a0 + a1) + a1 lambda, a0 = d0 + d1 u
-    uint64_t q[4] = {k[0], k[1], k[2], k[3]};
-    const uint64_t d0 = divmod_u(q), d1 = divmod_u(q);   // q = a1 < 2^128
-    u128h a0 = (u128h)d1 * Z_ABS_H + d0, a1 = (u128h)q[1] << 64 | q[0];
-    u128h s = a0 + a1;
-    const uint64_t s_top = s < a0 ? 1 : 0;
-    const uint64_t k1[3] = {(uint64_t)s, (uint64_t)(s >> 64), s_top}, k2[2] = {(uint64_t)a1, (uint64_t)(a1 >> 64)};
-    const u128h zz = (u128h)Z_ABS_H * Z_ABS_H;
-    fph::g1a phiP;
-    fph::g1_phi(phiP, P);
-    {   // membership on the host: [z^2] P == P + phi(P) = (beta^2 x, -y) (128 doublings of host field code)
-        fph::g1 m, PJ;
-        fph::jac_from_aff(PJ, P);
-        fph::jac_set_inf(m);
-        for (int b = 127; b >= 0; b--) {
-            fph::jac_dbl(m, m);
-            if ((zz >> b) & 1) fph::jac_add(m, m, PJ);
-        }
-        fph::g1a chk;
-        fph::g1_phi(chk, phiP);                   // (beta^2 x, y)
-        fph::neg(chk.y, chk.y);
-        if (!fph::jac_eq_aff(m, chk)) {           // outside G1: the split does not apply
-            g1_op(OP_G1_MUL, z, x, nullptr, y);
-            return;
-        }
-    }
-    // four ladders of <= 65 bits: k1 = k1_lo + 2^65 k1_hi over P and [2^65] P, k2 likewise over phi(P) and
-    // [2^65] phi(P) = phi([2^65] P) (the doublings on the host): half the serial rounds of two 129-bit ladders
-    fph::g1a P65, phiP65;
-    {
-        fph::g1 t;
-        fph::jac_from_aff(t, P);
-        for (int i = 0; i < 65; i++) fph::jac_dbl(t, t);
-        fph::jac_to_aff(P65, t);
-        fph::g1_phi(phiP65, P65);
-    }
-    if (P65.inf) { g1_op(OP_G1_MUL, z, x, nullptr, y); return; }    // unreachable in G1 (2^65 < r)
-    const uint64_t k1lo[2] = {k1[0], k1[1] & 1}, k1hi[2] = {(k1[1] >> 1) | (k1[2] << 63), k1[2] >> 1};
-    const uint64_t k2lo[2] = {k2[0], k2[1] & 1}, k2hi[2] = {k2[1] >> 1, 0};
-    PtJobG1 jobs[4];
-    memset(jobs, 0, sizeof jobs);
-    put_point(jobs[0], P);
-    put_point(jobs[1], P65);
-    put_point(jobs[2], phiP);
-    put_point(jobs[3], phiP65);
-    if (!put_digits(jobs[0], k1lo, 2, 18) || !put_digits(jobs[1], k1hi, 2, 18) || !put_digits(jobs[2], k2lo, 2, 18) ||
-        !put_digits(jobs[3], k2hi, 2, 18)) {
-        g1_op(OP_G1_MUL, z, x, nullptr, y);       // unreachable (< 2^66 in 18 signed windows): the exact ladder
-        return;
-    }
-    fph::g1 acc[4];
-    if (!ptmul_run(1, jobs, sizeof(PtJobG1), 4, acc, sizeof(fph::g1))) { fail_out(z, 144); return; }
-    fph::g1 r;
-    fph::jac_add(r, acc[0], acc[1]);
-    fph::jac_add(r, r, acc[2]);
-    fph::jac_add(r, r, acc[3]);
-    *G1W(z) = r;
-}
-extern "C" void lcb_g1_generator(mclBnG1 *g) { fph::g1_generator(*G1W(g)); }
-
-extern "C" mclSize mclBnG2_serialize(void *buf, mclSize max, const mclBnG2 *x) {
-    if (max < 96) return 0;
-    fph::g2_compress((uint8_t *)buf, *G2R(x), g_g2_sign_b.load() != 0);
-    return 96;
-}
-extern "C" mclSize mclBnG2_deserialize(mclBnG2 *x, const void *buf, mclSize n) {
-    if (n < 96) return 0;
-    fph::g2a a;
-    if (!fph::g2_decompress(a, (const uint8_t *)buf, g_g2_sign_b.load() != 0)) return 0;
-    fph::jac_from_aff(*G2W(x), a);
-    return 96;
-}
-extern "C" int mclBnG2_isValid(const mclBnG2 *x) { return fph::jac_valid(*G2R(x)); }
-extern "C" int mclBnG2_isEqual(const mclBnG2 *x, const mclBnG2 *y) { return fph::jac_eq(*G2R(x), *G2R(y)); }
-extern "C" int mclBnG2_isZero(const mclBnG2 *x) {
-    static const u32 z[24] = {0};
-    return memcmp(&x->z, z, 96) == 0;
-}
-extern "C" void mclBnG2_clear(mclBnG2 *x) { memset(x, 0, sizeof *x); }
-extern "C" int mclBnG2_hashAndMapTo(mclBnG2 *x, const void *buf, mclSize n) {
-    if (n > (IO_WORDS - 256) * 4) { set_err("message too long"); return -1; }
-    LOCKED_OR(-1)
-    IOH[250] = (u32)n;
-    memcpy(IOH + 256, buf, n);
-    if (!run_hash(256 + (n + 3) / 4, 249) || !IOH[248]) return -1;
-    memcpy(x, IOH, 288);
-    return 0;
-}
-static void g2_op(int op, mclBnG2 *z, const mclBnG2 *x, const mclBnG2 *y, const mclBnFr *k) {
-    if (!stage_ready()) { fail_out(z, 288); return; }
-    memcpy(IOH + 72, x, 288);
-    if (y) memcpy(IOH + 144, y, 288);
-    if (k) memcpy(IOH + 216, k, 32);
-    if (run_op(op, 224, 72)) memcpy(z, IOH, 288);
-    else fail_out(z, 288);
-}
-extern "C" void mclBnG2_neg(mclBnG2 *y, const mclBnG2 *x) { fph::jac_neg(*G2W(y), *G2R(x)); }
-extern "C" void mclBnG2_dbl(mclBnG2 *y, const mclBnG2 *x) { fph::g2 t; fph::jac_dbl(t, *G2R(x)); *G2W(y) = t; }
-extern "C" void mclBnG2_normalize(mclBnG2 *y, const mclBnG2 *x) { fph::jac_normalize(*G2W(y), *G2R(x)); }
-extern "C" void mclBnG2_add(mclBnG2 *z, const mclBnG2 *x, const mclBnG2 *y) {
-    fph::g2 t;
-    fph::jac_add(t, *G2R(x), *G2R(y));
-    *G2W(z) = t;
-}
-extern "C" void mclBnG2_sub(mclBnG2 *z, const mclBnG2 *x, const mclBnG2 *y) {
-    fph::g2 ny, t;
-    fph::jac_neg(ny, *G2R(y));
-    fph::jac_add(t, *G2R(x), ny);
-    *G2W(z) = t;
-}
-extern "C" void mclBnG2_mul(mclBnG2 *z, const mclBnG2 *x, const mclBnFr *y) {
-    uint64_t k[4];
-    frh::to_raw(k, FRV(y));
-    fph::g2a Q;
-    fph::jac_to_aff(Q, *G2R(x));
-    if (Q.inf || (k[0] | k[1] | k[2] | k[3]) == 0 || !fph::jac_on_curve(*G2R(x))) {
-        if (Q.inf || (k[0] | k[1] | k[2] | k[3]) == 0) { fph::jac_set_inf(*G2W(z)); return; }
-        g2_op(OP_G2_MUL, z, x, nullptr, y);
-        return;
-    }
-    // GLS (curve.hpp g2_mul_gls): k = d0 + d1 u + d2 u^2 + d3 u^3 over Q, -psi Q, psi^2 Q, -psi^3 Q
-    uint64_t q[4] = {k[0], k[1], k[2], k[3]}, d[4];
-    d[0] = divmod_u(q);
-    d[1] = divmod_u(q);
-    d[2] = divmod_u(q);
-    d[3] = q[0];                                  // k < r < u^4
-    fph::g2a B[4];
-    B[0] = Q;
-    fph::g2_psi(B[1], Q);
-    fph::g2_psi(B[2], B[1]);
-    fph::g2_psi(B[3], B[2]);
-    fph::g2a psiQ = B[1];
-    {   // membership on the host: psi(Q) == -[|z|] Q (64 doublings of host field code)
-        fph::g2 m, QJ;
-        fph::jac_from_aff(QJ, Q);
-        fph::jac_set_inf(m);
-        for (int b = 63; b >= 0; b--) {
-            fph::jac_dbl(m, m);
-            if ((Z_ABS_H >> b) & 1) fph::jac_add(m, m, QJ);
-        }
-        fph::g2a chk = psiQ;
-        fph::neg(chk.y, chk.y);
-        if (!fph::jac_eq_aff(m, chk)) {           // outside G2: the split does not apply
-            g2_op(OP_G2_MUL, z, x, nullptr, y);
-            return;
-        }
-    }
-    // eight ladders of 32 bits: each digit d_i = lo + 2^32 hi over B_i and [2^32] B_i (= +-psi^i([2^32] Q), the
-    // doublings on the host): half the serial rounds of four 64-bit ladders
-    fph::g2a Q32, C[4];
-    {
-        fph::g2 t;
-        fph::jac_from_aff(t, Q);
-        for (int i = 0; i < 32; i++) fph::jac_dbl(t, t);
-        fph::jac_to_aff(Q32, t);
-    }
-    if (Q32.inf) { g2_op(OP_G2_MUL, z, x, nullptr, y); return; }    // unreachable in G2 (2^32 < r)
-    C[0] = Q32;
-    fph::g2_psi(C[1], Q32);
-    fph::g2_psi(C[2], C[1]);
-    fph::g2_psi(C[3], C[2]);
-    fph::neg(C[1].y, C[1].y);
-    fph::neg(C[3].y, C[3].y);
-    fph::neg(B[1].y, B[1].y);
-    fph::neg(B[3].y, B[3].y);
-    PtJobG2 jobs[8];
-    memset(jobs, 0, sizeof jobs);
-    bool dig_ok = true;
-    for (int i = 0; i < 4; i++) {
-        const uint64_t lo = d[i] & 0xffffffffull, hi = d[i] >> 32;
-        put_point(jobs[2 * i], B[i]);
-        put_point(jobs[2 * i + 1], C[i]);
-        dig_ok &= put_digits(jobs[2 * i], &lo, 1, 9);
-        dig_ok &= put_digits(jobs[2 * i + 1], &hi, 1, 9);
-    }
-    if (!dig_ok) { g2_op(OP_G2_MUL, z, x, nullptr, y); return; }   // unreachable (32-bit digits): the exact ladder
-    fph::g2 acc[8];
-    if (!ptmul_run(2, jobs, sizeof(PtJobG2), 8, acc, sizeof(fph::g2))) { fail_out(z, 288); return; }
-    fph::g2 r = acc[0];
-    for (int i = 1; i < 8; i++) fph::jac_add(r, r, acc[i]);
-    *G2W(z) = r;
-}
-extern "C" void lcb_g2_generator(mclBnG2 *g) { fph::g2_generator(*G2W(g)); }
-
-// ================================================================== GT / pairing
-static void pair_op(int op, mclBnGT *z, const mclBnG1 *x, const mclBnG2 *y) {
-    if (!stage_ready()) { fail_out(z, 576); return; }
-    memcpy(IOH + 144, x, 144);
-    memcpy(IOH + 180, y, 288);
-    if (run_op(op, 252, 144)) memcpy(z, IOH, 576);
-    else fail_out(z, 576);
-}
-extern "C" void mclBn_millerLoop(mclBnGT *z, const mclBnG1 *x, const mclBnG2 *y) { pair_op(OP_MILLER, z, x, y); }
-static void gt_op(int op, mclBnGT *z, const mclBnGT *a, const mclBnGT *b, const mclBnFr *k) {
-    if (!stage_ready()) { fail_out(z, 576); return; }
-    memcpy(IOH + 252, a, 576);
-    if (b) memcpy(IOH + 396, b, 576);
-    if (k) memcpy(IOH + 540, k, 32);
-    if (run_op(op, 548, 144)) memcpy(z, IOH, 576);
-    else fail_out(z, 576);
-}
-extern "C" void mclBn_millerLoopVec(mclBnGT *z, const mclBnG1 *x, const mclBnG2 *y, mclSize n) {
-    mclBnGT acc, t;
-    memset(&acc, 0, sizeof acc);
-    const uint64_t errs = g_err_count;
-    for (mclSize i = 0; i < n && g_err_count == errs; i++) {
-        mclBn_millerLoop(&t, &x[i], &y[i]);
-        if (i == 0) acc = t;
-        else mclBnGT_mul(&acc, &acc, &t);
-    }
-    if (g_err_count != errs) fail_out(&acc, 576);
-    *z = acc;
-}
-// debug-only (not in include/lachain_bls.h): apply tower routine `which` (k_ops.hip OP_DEBUG_FP12) to raw GT words
-extern "C" int lcb_debug_fp12(int which, const uint32_t in[144], uint32_t out[144]) {
-    LOCKED_OR(-1)
-    memcpy(IOH + 252, in, 576);
-    IOH[548] = (u32)which;
-    if (!run_op(OP_DEBUG_FP12, 549, 144)) return -1;
-    memcpy(out, IOH, 576);
-    return 0;
-}
-extern "C" void mclBnGT_mul(mclBnGT *z, const mclBnGT *x, const mclBnGT *y) {
-    fph::fp12 t;
-    fph::mul(t, *(const fph::fp12 *)x, *(const fph::fp12 *)y);
-    memcpy(z, &t, 576);
-}
-extern "C" void mclBnGT_pow(mclBnGT *z, const mclBnGT *x, const mclBnFr *y) { gt_op(OP_GT_POW, z, x, nullptr, y); }
-extern "C" int mclBnGT_isEqual(const mclBnGT *x, const mclBnGT *y) { return memcmp(x, y, 576) == 0; }
-extern "C" int mclBnGT_isOne(const mclBnGT *x) {
-    // Montgomery one of Fp in the first coordinate, zero elsewhere
-    const u32 *w = (const u32 *)x;
-    if (memcmp(w, LCB_ONE_HOST, 48) != 0) return 0;
-    for (int i = 12; i < 144; i++) if (w[i]) return 0;
-    return 1;
-}
-extern "C" int mclBnGT_isZero(const mclBnGT *x) {
-    const u32 *w = (const u32 *)x;
-    for (int i = 0; i < 144; i++) if (w[i]) return 0;
-    return 1;
-}
-extern "C" void mclBnGT_clear(mclBnGT *x) { memset(x, 0, sizeof *x); }
-extern "C" mclSize mclBnGT_serialize(void *buf, mclSize max, const mclBnGT *x) {
-    if (max < 576) return 0;
-    const fph::fp *a = (const fph::fp *)x;
-    uint8_t *b = (uint8_t *)buf;
-    for (int i = 0; i < 12; i++) {
-        fph::fp r;
-        fph::to_raw(r, a[i]);
-        memcpy(b + 48 * i, r.v, 48);
-    }
-    return 576;
-}
-extern "C" mclSize mclBnGT_deserialize(mclBnGT *x, const void *buf, mclSize n) {
-    if (n < 576) return 0;
-    fph::fp m[12];
-    for (int i = 0; i < 12; i++) {
-        fph::fp raw;
-        memcpy(raw.v, (const uint8_t *)buf + 48 * i, 48);
-        if (!fph::raw_lt_p(raw)) return 0;
-        fph::from_raw(m[i], raw);
-    }
-    memcpy(x, m, 576);
-    return 576;
-}
-extern "C" int lcb_set_g2_sign_from_b(int use_b) {
-    // unpinned mcl convention: which coordinate's parity the G2 wire flag carries.  Applies to every
-    // later call, host (de)serialization and every kernel that (de)compresses G2 points alike; call it before any
-    // batch work, not while one is running.
-    if (!ready()) return -1;
-    g_g2_sign_b.store(use_b != 0);
-    if (lcbk_set_g2_sign_b(use_b != 0)) { set_err("lcb_set_g2_sign_from_b: device configuration failed"); return -1; }
-    return 0;
-}
-
-// ================================================================== Fr Lagrange / polynomials (host, fr_host.hpp)
-extern "C" int mclBn_FrLagrangeInterpolation(mclBnFr *out, const mclBnFr *xVec, const mclBnFr *yVec, mclSize k) {
-    // mcl LagrangeInterpolation: sum_i y_i prod_{j != i} x_j / (x_j - x_i); zero or repeated x is an error
-    if (k == 0) return -1;
-    for (mclSize i = 0; i < k; i++) {
-        if (mclBnFr_isZero(&xVec[i])) return -1;
-        for (mclSize j = 0; j < i; j++)
-            if (mclBnFr_isEqual(&xVec[i], &xVec[j])) return -1;
-    }
-    if (k == 1) { *out = yVec[0]; return 0; }
-    mclBnFr a, acc, t, d;
-    memcpy(&a, &xVec[0], 32);
-    for (mclSize i = 1; i < k; i++) mclBnFr_mul(&a, &a, &xVec[i]);
-    mclBnFr_clear(&acc);
-    for (mclSize i = 0; i < k; i++) {
-        mclBnFr b = xVec[i];
-        for (mclSize j = 0; j < k; j++) {
-            if (j == i) continue;
-            mclBnFr_sub(&d, &xVec[j], &xVec[i]);
-            mclBnFr_mul(&b, &b, &d);
-        }
-        mclBnFr_div(&t, &a, &b);
-        mclBnFr_mul(&t, &t, &yVec[i]);
-        mclBnFr_add(&acc, &acc, &t);
-    }
-    *out = acc;
-    return 0;
-}
-extern "C" int mclBn_FrEvaluatePolynomial(mclBnFr *out, const mclBnFr *c, mclSize n, const mclBnFr *x) {
-    if (n == 0) return -1;
-    mclBnFr acc = c[n - 1];
-    for (mclSize i = n - 1; i-- > 0;) {
-        mclBnFr_mul(&acc, &acc, x);
-        mclBnFr_add(&acc, &acc, &c[i]);
-    }
-    *out = acc;
-    return 0;
-}
-
 // line sets of n points a prepare kernel (or the host) stored in their sets: the five-lane kernel (k_lines.hip, ~1.5 ms
 // of latency) for the small preparations the single calls and the aggregation queue make, one lane per set (~4 ms of
 // latency, but about half the work per set) for large batches
@@ -1053,13 +412,17 @@ lcb_ctx *ctx_new() {
 }
 // each thread owns two implicit contexts: one for the *_dev entry points without a context argument, one for the
 // synchronous host-pointer entry points (so a host-pointer call never touches a workspace a *_dev caller prepared)
+std::mutex &retired_mu() {                           // the list's own lock, leaked like the list
+    static std::mutex *m = new std::mutex;
+    return *m;
+}
 std::vector<lcb_ctx *> &retired_ctxs() {
     static std::vector<lcb_ctx *> *v = new std::vector<lcb_ctx *>;
     return *v;
 }
 struct ThreadCtx {
     lcb_ctx *c = nullptr;
-    ~ThreadCtx() {                                   // retired, not freed (see OpStage)
+    ~ThreadCtx() {                                   // retired, not freed (see lcb_mcl.cpp OpStage)
         if (!c) return;
         std::lock_guard<std::mutex> lk(retired_mu());
         retired_ctxs().push_back(c);
@@ -1085,7 +448,8 @@ lcb_ctx *implicit_ctx_new() {
     }
     return ctx_new();
 }
-lcb_ctx *resolve(lcb_ctx *c) {
+} // namespace
+lcb_ctx *lcb_int::ctx_resolve(lcb_ctx *c) {
     if (!ready()) return nullptr;
     if (c) {
         if (c->device != g_device) { set_err("context belongs to another device"); return nullptr; }
@@ -1094,35 +458,23 @@ lcb_ctx *resolve(lcb_ctx *c) {
     if (!t_dev_ctx.c) t_dev_ctx.c = implicit_ctx_new();
     return t_dev_ctx.c;
 }
-lcb_ctx *sync_ctx() {
+lcb_ctx *lcb_int::ctx_sync() {
     if (!ready()) return nullptr;
     if (!t_sync_ctx.c) t_sync_ctx.c = implicit_ctx_new();
     return t_sync_ctx.c;
 }
-
-#define CTX_OR(var, ctxarg, ret)                 \
-    lcb_ctx *var = resolve(ctxarg);              \
-    if (!var) return ret;
-#define SYNC_CTX_OR(var, ret)                    \
-    lcb_ctx *var = sync_ctx();                   \
-    if (!var) return ret;
-
-template <class T> T *up(DevBuf &b, const T *src, size_t count, hipStream_t s) {
-    T *d = (T *)b.get(count * sizeof(T));
-    if (d && count) hipMemcpyAsync(d, src, count * sizeof(T), hipMemcpyHostToDevice, s);
-    return d;
-}
-bool launched(const char *what) {
+bool lcb_int::launch_ok(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_err(what, e); return false; }
     return true;
 }
-bool sync_check(lcb_ctx *c, const char *what) {
+bool lcb_int::sync_check(lcb_ctx *c, const char *what) {
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { set_err(what, e); return false; }
     return true;
 }
+namespace {
 
 // ------------------------------------------------------------------ TPKE
 // shares / checks per Miller + final-exponentiation launch pair (bounds the park buffers); lcb_set_verify_chunk (test
@@ -1151,7 +503,7 @@ int tpke_prepare(lcb_ctx *c, const uint8_t *d_y, size_t n_keys, const uint8_t *d
     }
     c->unn_census = 1;
     lines_flag_enqueue(c, 1, lines, 0, (u32)n_cts, s);
-    if (!launched("tpke prepare launch")) return -1;
+    if (!launch_ok("tpke prepare launch")) return -1;
     c->t_n_cts = n_cts;
     c->t_n_keys = n_keys;
     c->t_gen++;
@@ -1199,7 +551,7 @@ int tpke_verify_core(lcb_ctx *c, const u32 *lines, const uint8_t *ctok, size_t n
         }
         c->ver_ran = true;
     }
-    return launched("tpke verify launch") ? 0 : -1;
+    return launch_ok("tpke verify launch") ? 0 : -1;
 }
 int tpke_verify_prepared(lcb_ctx *c, uint8_t *d_accept, size_t n, size_t n_keys, size_t n_cts, const uint32_t *d_ct,
                          const uint32_t *d_dec, const uint8_t *d_ui, hipStream_t s) {
@@ -1218,7 +570,7 @@ int tpke_partial_decrypt_prepared(lcb_ctx *c, uint8_t *ui_out, uint8_t *status, 
         lcbk_final_exp_check(dim3(nblk(m)), s, f, (u32)m, status + o);
         lcbk_tpke_pd_mul(s, cts_u, x_raw, (u32)x_stride, (u32)o, (u32)m, status, ui_out);
     }
-    return launched("tpke partial decrypt launch") ? 0 : -1;
+    return launch_ok("tpke partial decrypt launch") ? 0 : -1;
 }
 
 
@@ -1233,7 +585,7 @@ int ts_prepare(lcb_ctx *c, const uint8_t *d_pks, size_t n_pks, const uint8_t *d_
     if (!lines || !mok || !keys) { set_err("device allocation failed"); return -1; }
     if (n_pks) lcbk_g1_decompress(dim3(nblk(n_pks)), s, d_pks, (u32)n_pks, keys);
     if (n_msgs) lcbk_ts_msg_prepare(dim3(nblk(n_msgs)), s, d_msg, d_moff, (u32)n_msgs, lines, mok, prepare_flags());
-    if (!launched("ts prepare launch")) return -1;
+    if (!launch_ok("ts prepare launch")) return -1;
     c->s_n_msgs = n_msgs;
     c->s_n_pks = n_pks;
     c->s_gen++;
@@ -1257,14 +609,14 @@ int ts_verify_prepared(lcb_ctx *c, uint8_t *d_accept, size_t n, size_t n_pks, si
             lcbk_final_exp_check(dim3(nblk(m)), s, f, (u32)m, d_accept + o);
         }
     }
-    return launched("ts verify launch") ? 0 : -1;
+    return launch_ok("ts verify launch") ? 0 : -1;
 }
 
 // ------------------------------------------------------------------ Lagrange / assembly
 // device-side Lagrange at 0 for np problems (entries off[j]..off[j+1]); dout = serialized results, dst = status
-int lagrange_enqueue(lcb_ctx *c, int g, uint8_t *dout, uint8_t *dst, const uint8_t *dx, const uint8_t *dy,
-                     const uint32_t *doff, size_t np, size_t ne, hipStream_t s, const u32 *src = nullptr,
-                     bool pairs = false) {
+} // namespace
+int lcb_int::lagrange_enqueue(lcb_ctx *c, int g, uint8_t *dout, uint8_t *dst, const uint8_t *dx, const uint8_t *dy,
+                              const uint32_t *doff, size_t np, size_t ne, hipStream_t s, const u32 *src, bool pairs) {
     if (np > 0xffffffffu || ne > 0xffffffffu) { set_err("lagrange: batch too large"); return -1; }
     void *lam = c->lag[0].get(LCB_FR_BYTES * (ne ? ne : 1));
     void *pre = c->lag[4].get(LCB_FR_BYTES * (ne ? ne : 1));      // the batch inversion's prefix products
@@ -1285,8 +637,9 @@ int lagrange_enqueue(lcb_ctx *c, int g, uint8_t *dout, uint8_t *dst, const uint8
     }
     if (g == 1) lcbk_g1_sum(dim3(nblk(np)), s, parts, pok, doff, (u32)np, dst, dout);
     else lcbk_g2_sum(dim3(nblk(np)), s, parts, pok, doff, (u32)np, dst, dout);
-    return launched("lagrange launch") ? 0 : -1;
+    return launch_ok("lagrange launch") ? 0 : -1;
 }
+namespace {
 int assemble_enqueue(lcb_ctx *c, int g, uint8_t *out, uint8_t *status, const uint8_t *accept, const uint8_t *pts,
                      size_t per_group, size_t k, size_t n_groups, hipStream_t s, const uint32_t *order = nullptr) {
     if (!n_groups) return 0;
@@ -1419,7 +772,7 @@ int msm_enqueue(lcb_ctx *cx, void *out_jac, const void *pts, const uint8_t *scal
     lcbk_msm_horner(s, wins, nwin, c, glv ? 1u : 0u, out_jac);
     hipEventRecord(cx->msm_ev[6], s);
     cx->msm_ran = true;
-    return launched("msm launch") ? 0 : -1;
+    return launch_ok("msm launch") ? 0 : -1;
 }
 
 } // namespace
@@ -2077,270 +1430,7 @@ extern "C" int lcb_coin_fold_dev(uint8_t *parity, uint64_t *nonce, const uint8_t
     if (!ready()) return -1;
     if (n > 0xffffffffu) { set_err("coin fold: batch too large"); return -1; }
     if (n) lcbk_coin_fold(dim3(nblk(n)), (hipStream_t)stream, sigs, (u32)n, parity, nonce);
-    return launched("coin fold launch") ? 0 : -1;
-}
-
-// ================================================================== trustless DKG G1 work (k_dkg.hip)
-// Commitment.Evaluate(x, y) / Evaluate(x) (src/Lachain.Consensus/ThresholdKeygen/Data/Commitment.cs:23-53) for whole
-// batches: rows of every distinct (commitment, x) once, then Horner in y per query.
-namespace {
-// any decodable point of d_aff (n records) outside G1 (k_g1_subgroup_any; one 4-byte read)
-int g1_any_off_subgroup(lcb_ctx *c, const void *d_aff, size_t n, hipStream_t s, bool *any) {
-    u32 *d = (u32 *)c->dkg[8].get(4);
-    if (!d) { set_err("device allocation failed"); return -1; }
-    hipMemsetAsync(d, 0, 4, s);
-    if (n) lcbk_g1_subgroup_any(s, d_aff, (u32)n, d);
-    u32 h = 0;
-    if (!launched("subgroup test launch")) return -1;
-    if (hipMemcpyAsync(&h, d, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-        set_err("batched verify: group count");
-        return -1;
-    }
-    *any = h != 0;
-    return 0;
-}
-// Commitment.Evaluate(x) rows of n_rows (commitment, x) pairs.  Honest commitments (every coefficient in G1): Horner in
-// the small x (k_dkg_rows).  A batch with a coefficient outside G1: the reference's own terms [x^j mod r] C (exact).
-int dkg_rows_enqueue(lcb_ctx *c, const uint8_t *d_coeffs, size_t n_comm, size_t n_coef, int degree,
-                     const uint32_t *d_comm, const int32_t *d_xs, size_t n_rows, hipStream_t s, void **rows_out,
-                     uint8_t **rows_ok, bool *exact) {
-    size_t total = n_comm * n_coef, lanes = n_rows * (size_t)(degree + 1);
-    if (total > 0xffffffffu || lanes > 0xffffffffu) { set_err("dkg: batch too large"); return -1; }
-    void *aff = c->dkg[0].get(total * LCB_G1A_ST_BYTES);
-    void *rows = c->dkg[1].get(lanes * LCB_G1_JAC_BYTES);
-    uint8_t *rok = (uint8_t *)c->dkg[2].get(lanes);
-    if (!aff || !rows || !rok) { set_err("device allocation failed"); return -1; }
-    if (total) lcbk_g1_decompress(dim3(nblk(total)), s, d_coeffs, (u32)total, aff);
-    if (g1_any_off_subgroup(c, aff, total, s, exact)) return -1;
-    if (lanes && !*exact) {
-        lcbk_dkg_rows(dim3(nblk(lanes)), s, aff, (u32)n_coef, (u32)n_comm, (u32)degree, d_comm, d_xs, (u32)n_rows, rows,
-                      rok);
-    } else if (lanes) {
-        const size_t nt = lanes * (size_t)(degree + 1);
-        if (nt > 0xffffffffu) { set_err("dkg: batch too large for the exact form"); return -1; }
-        void *terms = c->dkg[6].get(nt * LCB_G1_JAC_BYTES);
-        uint8_t *tok = (uint8_t *)c->dkg[7].get(nt);
-        if (!terms || !tok) { set_err("device allocation failed"); return -1; }
-        lcbk_dkg_exact_terms(s, aff, (u32)n_coef, (u32)n_comm, (u32)degree, d_comm, d_xs, (u32)n_rows, terms, tok);
-        lcbk_g1_jac_reduce_groups(dim3(nblk(lanes)), s, terms, (u32)nt, (u32)(degree + 1), rows);
-        lcbk_and_groups(s, tok, (u32)lanes, (u32)(degree + 1), rok);
-    }
-    *rows_out = rows;
-    *rows_ok = rok;
-    return launched("dkg rows launch") ? 0 : -1;
-}
-bool dkg_shape(size_t n_comm, int degree, size_t *n_coef) {
-    if (degree < 0 || degree > 4096) { set_err("dkg: degree out of range"); return false; }
-    *n_coef = (size_t)(degree + 1) * (size_t)(degree + 2) / 2;
-    (void)n_comm;
-    return true;
-}
-}  // namespace
-extern "C" int lcb_dkg_commitment_rows(uint8_t *rows_out, uint8_t *status, const uint8_t *coeffs, size_t n_comm,
-                                       int degree, const uint32_t *comm_idx, const int32_t *xs, size_t n_queries) {
-    SYNC_CTX_OR(c, -1)
-    size_t n_coef;
-    if (!dkg_shape(n_comm, degree, &n_coef)) return -1;
-    if (!n_queries) return 0;
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    size_t lanes = n_queries * (size_t)(degree + 1);
-    const uint8_t *dco = up(c->in[0], coeffs, 48 * n_comm * n_coef, s);
-    const uint32_t *dci = up(c->in[1], comm_idx, n_queries, s);
-    const int32_t *dx = up(c->in[2], xs, n_queries, s);
-    uint8_t *dout = (uint8_t *)c->out[0].get(48 * lanes);
-    if (!dco || !dci || !dx || !dout) { set_err("device allocation failed"); return -1; }
-    void *rows;
-    uint8_t *rok;
-    bool exact = false;
-    if (dkg_rows_enqueue(c, dco, n_comm, n_coef, degree, dci, dx, n_queries, s, &rows, &rok, &exact)) return -1;
-    lcbk_g1_jac_compress(dim3(nblk(lanes)), s, rows, (u32)lanes, dout);
-    std::vector<uint8_t> ok(lanes);
-    hipMemcpyAsync(rows_out, dout, 48 * lanes, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(ok.data(), rok, lanes, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "dkg rows")) return -1;
-    for (size_t qi = 0; qi < n_queries; qi++) {
-        uint8_t st = 1;
-        for (int i = 0; i <= degree; i++) st &= ok[qi * (degree + 1) + i];
-        status[qi] = st;
-    }
-    return 0;
-}
-extern "C" int lcb_dkg_commitment_eval(uint8_t *out, uint8_t *status, const uint8_t *coeffs, size_t n_comm, int degree,
-                                       const uint32_t *comm_idx, const int32_t *xs, const int32_t *ys,
-                                       size_t n_queries) {
-    SYNC_CTX_OR(c, -1)
-    size_t n_coef;
-    if (!dkg_shape(n_comm, degree, &n_coef)) return -1;
-    if (!n_queries) return 0;
-    // distinct (commitment, x) pairs -> rows; every query evaluates its row at y
-    std::vector<uint32_t> row_comm, row_of(n_queries);
-    std::vector<int32_t> row_x;
-    {
-        std::vector<std::pair<uint64_t, uint32_t>> keys(n_queries);
-        for (size_t i = 0; i < n_queries; i++) keys[i] = {((uint64_t)comm_idx[i] << 32) | (uint32_t)xs[i], (uint32_t)i};
-        std::sort(keys.begin(), keys.end());
-        for (size_t i = 0; i < n_queries; i++) {
-            if (i == 0 || keys[i].first != keys[i - 1].first) {
-                row_comm.push_back((uint32_t)(keys[i].first >> 32));
-                row_x.push_back((int32_t)(uint32_t)keys[i].first);
-            }
-            row_of[keys[i].second] = (uint32_t)(row_comm.size() - 1);
-        }
-    }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const uint8_t *dco = up(c->in[0], coeffs, 48 * n_comm * n_coef, s);
-    const uint32_t *drc = up(c->in[1], row_comm.data(), row_comm.size(), s);
-    const int32_t *drx = up(c->in[2], row_x.data(), row_x.size(), s);
-    const uint32_t *drow = up(c->in[3], row_of.data(), n_queries, s);
-    const int32_t *dy = up(c->in[4], ys, n_queries, s);
-    uint8_t *dout = (uint8_t *)c->out[0].get(48 * n_queries), *dst = (uint8_t *)c->out[1].get(n_queries);
-    if (!dco || !drc || !drx || !drow || !dy || !dout || !dst) { set_err("device allocation failed"); return -1; }
-    void *rows;
-    uint8_t *rok;
-    bool exact = false;
-    if (dkg_rows_enqueue(c, dco, n_comm, n_coef, degree, drc, drx, row_comm.size(), s, &rows, &rok, &exact)) return -1;
-    if (!exact) {
-        lcbk_dkg_horner(dim3(nblk(n_queries)), s, rows, rok, (u32)degree, drow, dy, (u32)n_queries, dout, dst, 0);
-        hipMemcpyAsync(out, dout, 48 * n_queries, hipMemcpyDeviceToHost, s);
-        hipMemcpyAsync(status, dst, n_queries, hipMemcpyDeviceToHost, s);
-        return sync_check(c, "dkg eval") ? 0 : -1;
-    }
-    // a coefficient outside G1: sum_j [y^j mod r] row_j(x) (Commitment.cs:23-37 as written)
-    const size_t D1 = (size_t)degree + 1, nt = n_queries * D1;
-    void *terms = c->dkg[6].get(nt * LCB_G1_JAC_BYTES), *sums = c->dkg[3].get(n_queries * LCB_G1_JAC_BYTES);
-    if (!terms || !sums) { set_err("device allocation failed"); return -1; }
-    lcbk_dkg_exact_combine(s, rows, (u32)degree, drow, dy, (u32)n_queries, terms);
-    lcbk_g1_jac_reduce_groups(dim3(nblk(n_queries)), s, terms, (u32)nt, (u32)D1, sums);
-    lcbk_g1_jac_compress(dim3(nblk(n_queries)), s, sums, (u32)n_queries, dout);
-    std::vector<uint8_t> rk(row_comm.size() * D1);
-    hipMemcpyAsync(out, dout, 48 * n_queries, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(rk.data(), rok, rk.size(), hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "dkg eval")) return -1;
-    for (size_t qi = 0; qi < n_queries; qi++) {
-        uint8_t st = 1;
-        for (size_t j = 0; j < D1; j++) st &= rk[row_of[qi] * D1 + j];
-        status[qi] = st;
-        if (!st) memset(out + 48 * qi, 0, 48);
-    }
-    return 0;
-}
-extern "C" int lcb_g1_eval_poly_batch(uint8_t *out, uint8_t *status, const uint8_t *coeffs, size_t n_coeffs,
-                                      const int32_t *xs, size_t n_points) {
-    SYNC_CTX_OR(c, -1)
-    if (!n_coeffs) { set_err("eval poly: no coefficients"); return -1; }
-    if (!n_points) return 0;
-    if (n_coeffs > 0xffffffffu || n_points > 0xffffffffu) { set_err("eval poly: batch too large"); return -1; }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const uint8_t *dco = up(c->in[0], coeffs, 48 * n_coeffs, s);
-    const int32_t *dx = up(c->in[1], xs, n_points, s);
-    void *aff = c->dkg[0].get(n_coeffs * LCB_G1A_ST_BYTES), *rows = c->dkg[1].get(n_coeffs * LCB_G1_JAC_BYTES);
-    uint8_t *rok = (uint8_t *)c->dkg[2].get(n_coeffs);
-    uint32_t *drow = (uint32_t *)c->dkg[3].get(4 * n_points);
-    uint8_t *dout = (uint8_t *)c->out[0].get(48 * n_points), *dst = (uint8_t *)c->out[1].get(n_points);
-    if (!dco || !dx || !aff || !rows || !rok || !drow || !dout || !dst) { set_err("device allocation failed"); return -1; }
-    hipMemsetAsync(drow, 0, 4 * n_points, s);    // every point evaluates row 0 (the coefficient vector)
-    lcbk_g1_decompress(dim3(nblk(n_coeffs)), s, dco, (u32)n_coeffs, aff);
-    bool off = false;                            // a coefficient outside G1: negative x multiply by Fr.FromInt(x)
-    bool neg = false;
-    for (size_t i = 0; i < n_points; i++) neg |= xs[i] < 0;
-    if (neg && g1_any_off_subgroup(c, aff, n_coeffs, s, &off)) return -1;
-    lcbk_g1a_to_jac(dim3(nblk(n_coeffs)), s, aff, (u32)n_coeffs, rows, rok);
-    lcbk_dkg_horner(dim3(nblk(n_points)), s, rows, rok, (u32)(n_coeffs - 1), drow, dx, (u32)n_points, dout, dst,
-                    off ? 1u : 0u);
-    hipMemcpyAsync(out, dout, 48 * n_points, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(status, dst, n_points, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "eval poly") ? 0 : -1;
-}
-
-// ================================================================== reliable-broadcast Reed-Solomon (k_rs.hip)
-// ReliableBroadcast.ErasureCodingShards / DecodeFromEchos (src/Lachain.Consensus/ReliableBroadcast/ReliableBroadcast.cs:
-// 393-446): the erased / parity shards are M times the known shards, M = H_E^-1 H_K built on the GPU.
-namespace {
-int rs_enqueue(lcb_ctx *c, uint8_t *d_out, const uint8_t *d_known, const std::vector<int> &pe,
-               const std::vector<int> &pk, int n, size_t S, hipStream_t s, uint8_t **d_ok) {
-    static bool attr = false;
-    if (!attr) {
-        hipFuncSetAttribute((const void *)lcbk_rs_matrix_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, 65536 * 2);
-        attr = true;
-    }
-    int m = (int)pe.size(), k = (int)pk.size();
-    int *dpe = (int *)c->dkg[4].get(4 * (pe.size() + pk.size()));
-    uint8_t *M = (uint8_t *)c->dkg[5].get((size_t)m * k + 16);
-    if (!dpe || !M) { set_err("device allocation failed"); return -1; }
-    std::vector<int> both(pe);
-    both.insert(both.end(), pk.begin(), pk.end());
-    hipMemcpyAsync(dpe, both.data(), 4 * both.size(), hipMemcpyHostToDevice, s);
-    uint8_t *ok = M + (size_t)m * k;
-    lcbk_rs_matrix(s, dpe, m, dpe + m, k, n, M, ok);
-    lcbk_rs_apply(s, M, ok, m, k, d_known, S, dpe, d_out);
-    *d_ok = ok;
-    return launched("rs launch") ? 0 : -1;
-}
-}  // namespace
-extern "C" int lcb_rs_encode(uint8_t *shards_out, const uint8_t *input, size_t input_len, int n_shards, int erasures) {
-    SYNC_CTX_OR(c, -1)
-    int k = n_shards - erasures;
-    if (n_shards <= 0 || erasures < 0 || k <= 0 || input_len % (size_t)k) {
-        set_err("rs encode: need 0 <= erasures < shards and input length divisible by the data shards");
-        return -1;
-    }
-    size_t S = input_len / (size_t)k;
-    if (erasures == 0 || S == 0) { memcpy(shards_out, input, input_len); return 0; }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    uint8_t *dout = (uint8_t *)c->out[0].get(S * n_shards);
-    if (!dout) { set_err("device allocation failed"); return -1; }
-    hipMemcpyAsync(dout, input, input_len, hipMemcpyHostToDevice, s);   // data shards stay in place (systematic)
-    std::vector<int> pe, pk;
-    for (int j = k; j < n_shards; j++) pe.push_back(j);
-    for (int j = 0; j < k; j++) pk.push_back(j);
-    uint8_t *dok;
-    if (rs_enqueue(c, dout, dout, pe, pk, n_shards, S, s, &dok)) return -1;
-    uint8_t ok = 0;
-    hipMemcpyAsync(shards_out, dout, S * n_shards, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(&ok, dok, 1, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "rs encode")) return -1;
-    if (!ok) { set_err("rs encode: parity positions are not independent (more than 255 shards)"); return -1; }
-    return 0;
-}
-extern "C" int lcb_rs_decode(uint8_t *out, const uint8_t *echo_data, const int32_t *from, int n_echos, size_t shard_size,
-                             int n_shards, int erasures) {
-    SYNC_CTX_OR(c, -1)
-    int k = n_shards - erasures;
-    if (n_shards <= 0 || erasures < 0 || k <= 0 || n_echos != k) {
-        set_err("rs decode: need exactly shards - erasures echoes (DecodeFromEchos asserts N - 2F)");
-        return -1;
-    }
-    std::vector<char> have(n_shards, 0);
-    std::vector<int> pe, pk;
-    for (int e = 0; e < n_echos; e++) {
-        if (from[e] < 0 || from[e] >= n_shards || have[from[e]]) { set_err("rs decode: bad or duplicate echo index"); return -1; }
-        have[from[e]] = 1;
-        pk.push_back(from[e]);
-    }
-    for (int j = 0; j < n_shards; j++) if (!have[j]) pe.push_back(j);
-    size_t S = shard_size;
-    if (S == 0) return 0;
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    uint8_t *dout = (uint8_t *)c->out[0].get(S * n_shards);
-    const uint8_t *decho = up(c->in[0], echo_data, S * (size_t)n_echos, s);
-    if (!dout || !decho) { set_err("device allocation failed"); return -1; }
-    for (int e = 0; e < n_echos; e++)
-        hipMemcpyAsync(dout + (size_t)from[e] * S, decho + (size_t)e * S, S, hipMemcpyDeviceToDevice, s);
-    uint8_t ok = 1;
-    if (!pe.empty()) {
-        uint8_t *dok;
-        if (rs_enqueue(c, dout, decho, pe, pk, n_shards, S, s, &dok)) return -1;
-        hipMemcpyAsync(&ok, dok, 1, hipMemcpyDeviceToHost, s);
-    }
-    hipMemcpyAsync(out, dout, S * n_shards, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "rs decode")) return -1;
-    if (!ok) { set_err("rs decode: erased positions share an evaluation point (more than 255 shards)"); return -1; }
-    return 0;
+    return launch_ok("coin fold launch") ? 0 : -1;
 }
 
 // ================================================================== batch: Lagrange, scalar mul, hash, MSM
@@ -2386,600 +1476,6 @@ extern "C" int lcb_g1_lagrange_batch(uint8_t *out, uint8_t *status, const uint8_
                                      const uint32_t *off, size_t n) { return lagrange_batch(1, out, status, xs, ys, off, n); }
 extern "C" int lcb_g2_lagrange_batch(uint8_t *out, uint8_t *status, const uint8_t *xs, const uint8_t *ys,
                                      const uint32_t *off, size_t n) { return lagrange_batch(2, out, status, xs, ys, off, n); }
-
-// ================================================================== mcl surface on the batch / cooperative kernels
-// (k_mcl.hip, k_coop.hip) — each a single synchronous call on the calling thread's own context
-
-#define LCB_PAIR_CACHE 32    // line-set slots per context (2 x 26 KB each)
-// mclBn_pairing (GT.Pairing: TPKE/PrivateKey.cs:26, TPKE/PublicKey.cs:91, ThresholdSignature/PublicKey.cs:20) as a
-// one-group cooperative check: P and the point at infinity, Q's normalised line set and the set of infinity, then
-// the nine-lane final exponentiation.  The lines are normalised (divided by their Fp2 leading coefficient), which
-// changes the Miller value by a factor the final exponentiation removes: the GT value is mcl's.
-// The line set of one G2 point on the host (pairing.hpp lineset_compute: the same 68 steps and formulas with the host
-// field code, which gives the kernels' canonical residues; the normalised lines B' = Bc / A, C' = Cc / A depend only on
-// the affine points, so they are the words k_lineset_coop writes).  False when some A_k == 0 (a point outside G2: the
-// caller then takes the kernel, whose Miller loop computes such a set's lines on the fly).
-static const bool g_pair_host_lines = !(getenv("LCB_PAIR_HOST_LINES") && atoi(getenv("LCB_PAIR_HOST_LINES")) == 0);
-static bool lineset_host(uint32_t *dst, const fph::g2a &Q) {
-    const int PT = LCB_LS_POINT_WORD, FLAG = PT + 48, NL = 68, NLW = 48;
-    memset(dst, 0, LCB_LINESET_BYTES);
-    memcpy(dst + PT, &Q.x, 96);
-    memcpy(dst + PT + 24, &Q.y, 96);
-    dst[FLAG + 1] = Q.inf ? 1u : 0u;
-    if (Q.inf) { dst[FLAG] = 1u; return true; }   // every line is the constant 1: B' = C' = 0
-    fph::fp twelve, raw12 = fph::zero();
-    raw12.v[0] = 12;
-    fph::from_raw(twelve, raw12);
-    fph::fp2 b3;                                  // 3 b' = 12 (1 + u)
-    b3.a = twelve;
-    b3.b = twelve;
-    fph::fp2 Tx = Q.x, Ty = Q.y, Tz = fph::one2();
-    std::vector<fph::fp2> A(NL), B(NL), C(NL);
-    int k = 0;
-    for (int i = 62; i >= 0; i--) {
-        {   // doubling step (ls_dbl_store): A = Y^2 - 3b'Z^2, Bc = -3X^2, Cc = 2YZ; T <- 2T
-            fph::fp2 YZ, XY, ZZ, YY, t, u;
-            fph::mul(YZ, Ty, Tz);
-            fph::mul(XY, Tx, Ty);
-            fph::sqr(ZZ, Tz);
-            fph::sqr(YY, Ty);
-            fph::sqr(t, Tx);
-            fph::add(u, t, t);
-            fph::add(u, u, t);
-            fph::neg(B[k], u);
-            fph::add(C[k], YZ, YZ);
-            fph::mul(Tz, YY, YZ);
-            fph::add(Tz, Tz, Tz);
-            fph::mul(ZZ, ZZ, b3);
-            fph::sub(A[k], YY, ZZ);
-            k++;
-            fph::add(t, ZZ, ZZ);
-            fph::add(t, t, ZZ);
-            fph::mul_fp(XY, XY, fph::INV2);
-            fph::sub(u, YY, t);
-            fph::mul(Tx, XY, u);
-            fph::add(u, YY, t);
-            fph::mul_fp(u, u, fph::INV2);
-            fph::sqr(Ty, u);
-            fph::sqr(t, ZZ);
-            fph::add(u, t, t);
-            fph::add(u, u, t);
-            fph::sub(Ty, Ty, u);
-        }
-        if ((Z_ABS_H >> i) & 1) {   // addition step (ls_add_store): A = th xQ - la yQ, Bc = -th, Cc = la; T <- T + Q
-            fph::fp2 th, la, t, D, E, G;
-            fph::mul(t, Q.y, Tz);
-            fph::sub(th, Ty, t);
-            fph::mul(t, Q.x, Tz);
-            fph::sub(la, Tx, t);
-            fph::mul(A[k], th, Q.x);
-            fph::mul(t, la, Q.y);
-            fph::sub(A[k], A[k], t);
-            fph::neg(B[k], th);
-            C[k] = la;
-            k++;
-            fph::sqr(D, la);
-            fph::mul(E, la, D);
-            fph::mul(G, Tx, D);
-            fph::sqr(t, th);
-            fph::mul(D, Tz, t);
-            fph::mul(Tz, Tz, E);
-            fph::add(D, E, D);
-            fph::sub(D, D, G);
-            fph::sub(D, D, G);
-            fph::mul(Tx, la, D);
-            fph::sub(t, G, D);
-            fph::mul(G, th, t);
-            fph::mul(t, Ty, E);
-            fph::sub(Ty, G, t);
-        }
-    }
-    if (k != NL) return false;
-    std::vector<fph::fp2> pre(NL);                // A_0 ... A_k, then one inversion (Montgomery's trick)
-    pre[0] = A[0];
-    for (int j = 1; j < NL; j++) fph::mul(pre[j], pre[j - 1], A[j]);
-    if (fph::is_zero(pre[NL - 1])) return false;
-    fph::fp2 inv;
-    fph::inv(inv, pre[NL - 1]);
-    for (int j = NL - 1; j >= 0; j--) {
-        fph::fp2 ai, b, c;
-        if (j > 0) fph::mul(ai, inv, pre[j - 1]);
-        else ai = inv;
-        fph::mul(inv, inv, A[j]);
-        fph::mul(b, B[j], ai);
-        fph::mul(c, C[j], ai);
-        memcpy(dst + j * NLW, &b, 96);
-        memcpy(dst + j * NLW + 24, &c, 96);
-    }
-    dst[FLAG] = 1u;
-    return true;
-}
-extern "C" void mclBn_pairing(mclBnGT *z, const mclBnG1 *x, const mclBnG2 *y) {
-    fail_out(z, 576);                  // overwritten on success; a failed call leaves a value no other call produces
-    if (injected(INJ_PAIRING_ALLOC)) { set_err("injected failure (pairing)"); return; }
-    SYNC_CTX_OR(c, )
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const size_t slots = lcbk_fe_slots() > 6 ? (size_t)lcbk_fe_slots() : 6;
-    // the group record (P and infinity, then the check's descriptor), staged in one copy
-    struct PairIn {
-        uint32_t g[2][LCB_G1A_ST_BYTES / 4];
-        uint32_t desc[4];
-    };
-    static_assert(sizeof(PairIn) == 2 * LCB_G1A_ST_BYTES + 16, "PairIn layout");
-    uint8_t *gin = (uint8_t *)c->mcl[1].get(sizeof(PairIn));
-    u32 *lines = (u32 *)c->pc_lines.get((size_t)2 * LCB_PAIR_CACHE * LCB_LINESET_BYTES);
-    u32 *park = (u32 *)c->mcl[4].get(576 * slots);
-    uint8_t *fl = (uint8_t *)c->mcl[5].get(64);
-    if (!gin || !lines || !park || !fl) { set_err("device allocation failed"); return; }
-    void *gpts = gin, *desc = gin + 2 * LCB_G1A_ST_BYTES;
-    if (c->pc_used.empty()) {
-        c->pc_keys.assign((size_t)72 * LCB_PAIR_CACHE, 0);
-        c->pc_used.assign(LCB_PAIR_CACHE, 0);
-    }
-    u32 slot = 0;
-    bool hit = false;
-    for (u32 k = 0; k < LCB_PAIR_CACHE; k++) {
-        if (c->pc_used[k] && memcmp(&c->pc_keys[72 * (size_t)k], y, 288) == 0) { slot = k; hit = true; break; }
-        if (c->pc_used[k] < c->pc_used[slot]) slot = k;
-    }
-    c->pc_used[slot] = ++c->pc_tick;
-    if (!hit) memcpy(&c->pc_keys[72 * (size_t)slot], y, 288);
-    // P and Q to affine on the calling thread (host inversions, tens of us) rather than in a one-lane kernel (~0.5 ms
-    // per inversion): the same canonical residues the device's jac_to_aff gives
-    PairIn pin;
-    memset(&pin, 0, sizeof pin);
-    {
-        fph::g1 P;
-        fph::g1a pa;
-        memcpy(&P, x, sizeof P);
-        fph::jac_to_aff(pa, P);
-        memcpy(&pin.g[0][0], &pa.x, 48);
-        memcpy(&pin.g[0][12], &pa.y, 48);
-        pin.g[0][24] = pa.inf ? 1u : 0u;
-        pin.g[0][25] = 1u;                           // ok
-        pin.g[1][24] = 1u;                           // the point at infinity
-        pin.g[1][25] = 1u;
-        pin.desc[0] = 0u;                            // check 0: points 0 and 1, line-set pair `slot`
-        pin.desc[1] = 1u;
-        pin.desc[2] = slot;
-    }
-    hipMemcpyAsync(gin, &pin, sizeof pin, hipMemcpyHostToDevice, s);
-    std::vector<uint32_t> hsets;                     // the host line sets (alive until the call's synchronisation)
-    bool host_sets = false;
-    if (!hit && g_pair_host_lines) {                 // Q's set and the infinity set computed here, one upload
-        fph::g2 Q;
-        fph::g2a qa, ia;
-        memcpy(&Q, y, sizeof Q);
-        fph::jac_to_aff(qa, Q);
-        memset(&ia, 0, sizeof ia);
-        ia.inf = true;
-        hsets.assign((size_t)2 * LCB_LINESET_BYTES / 4, 0u);
-        if (lineset_host(hsets.data(), qa) && lineset_host(hsets.data() + LCB_LINESET_BYTES / 4, ia)) {
-            hipMemcpyAsync(lines + (size_t)2 * slot * (LCB_LINESET_BYTES / 4), hsets.data(), 2 * (size_t)LCB_LINESET_BYTES,
-                           hipMemcpyHostToDevice, s);
-            host_sets = true;
-        }
-    }
-    if (!hit && !host_sets) {                        // the two sets' points for k_lineset_fill: Q, then infinity
-        fph::g2 Q;
-        fph::g2a qa;
-        memcpy(&Q, y, sizeof Q);
-        fph::jac_to_aff(qa, Q);
-        uint32_t pt[2][51];                          // x, y (48 words), LCB_LS_FLAG, + 1 (infinity), + 2 (force general)
-        memset(pt, 0, sizeof pt);
-        memcpy(&pt[0][0], &qa.x, 96);
-        memcpy(&pt[0][24], &qa.y, 96);
-        pt[0][49] = qa.inf ? 1u : 0u;
-        pt[1][49] = 1u;
-        for (int k = 0; k < 2; k++)
-            hipMemcpyAsync(lines + (size_t)(2 * slot + k) * (LCB_LINESET_BYTES / 4) + LCB_LS_POINT_WORD, pt[k],
-                           sizeof pt[k], hipMemcpyHostToDevice, s);
-    }
-    if (!hit && !host_sets) lcbk_lineset_coop(s, lines + (size_t)2 * slot * (LCB_LINESET_BYTES / 4), 2, nullptr, nullptr);
-    lcbk_coop_tpke_miller(s, lines, desc, gpts, 1, park, fl, fl + 32, 1, 1);
-    lcbk_coop_final_exp_check(s, park, 1, nullptr);
-    u32 r[144];
-    hipMemcpyAsync(r, park, 576, hipMemcpyDeviceToHost, s);
-    if (sync_check(c, "pairing")) memcpy(z, r, 576);
-    else c->pc_used[slot] = 0;                    // the slot's lines may be incomplete
-}
-// mclBn_finalExp on the nine-lane kernel (park slot 0 of a one-value workspace)
-extern "C" void mclBn_finalExp(mclBnGT *y, const mclBnGT *x) {
-    mclBnGT xin = *x;                  // y may alias x
-    x = &xin;
-    fail_out(y, 576);
-    SYNC_CTX_OR(c, )
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const size_t slots = lcbk_fe_slots() > 6 ? (size_t)lcbk_fe_slots() : 6;
-    u32 *park = (u32 *)c->mcl[4].get(576 * slots);
-    if (!park) { set_err("device allocation failed"); return; }
-    hipMemcpyAsync(park, x, 576, hipMemcpyHostToDevice, s);
-    lcbk_coop_final_exp_check(s, park, 1, nullptr);
-    u32 r[144];
-    hipMemcpyAsync(r, park, 576, hipMemcpyDeviceToHost, s);
-    if (sync_check(c, "final exp")) memcpy(y, r, 576);
-}
-// sum_i [k_i] x_i (canonical scalars k_i < r, raw words) on the cooperative ladders of mclBnG1_mul: three groups per
-// term (GLV halves over P and phi(P), and [z^2] P for the membership the split needs), k_ptmul_g1_multi, the terms
-// added on the host.  Returns 1 with *z set, 0 when a term is not on the curve or outside G1 (the caller then takes
-// its exact path, so every input keeps that path's value), -1 on a device error.
-static const size_t MULVEC_COOP_MAX = 512;
-static const bool g_mulvec_coop = !(getenv("LCB_MULVEC_COOP") && atoi(getenv("LCB_MULVEC_COOP")) == 0);
-static int g1_mulvec_coop(lcb_ctx *c, mclBnG1 *z, const mclBnG1 *x, const uint64_t (*kraw)[4], size_t n) {
-    std::vector<PtJobG1> jobs(3 * n);
-    memset(jobs.data(), 0, jobs.size() * sizeof(PtJobG1));
-    std::vector<fph::g1a> phis(n);
-    std::vector<uint8_t> live(n, 0);
-    const u128h zz = (u128h)Z_ABS_H * Z_ABS_H;
-    const uint64_t z2[2] = {(uint64_t)zz, (uint64_t)(zz >> 64)}, zero[1] = {0};
-    for (size_t i = 0; i < n; i++) {
-        PtJobG1 *J = &jobs[3 * i];
-        const uint64_t *k = kraw[i];
-        fph::g1a P;
-        fph::jac_to_aff(P, *G1R(&x[i]));
-        if (!P.inf && !fph::jac_on_curve(*G1R(&x[i]))) return 0;
-        if (P.inf || (k[0] | k[1] | k[2] | k[3]) == 0) {          // a zero term: three idle ladders
-            for (int j = 0; j < 3; j++) { J[j].inf = 1; put_digits(J[j], zero, 1, 33); }
-            continue;
-        }
-        uint64_t q[4] = {k[0], k[1], k[2], k[3]};
-        const uint64_t d0 = divmod_u(q), d1 = divmod_u(q);
-        const u128h a0 = (u128h)d1 * Z_ABS_H + d0, a1 = (u128h)q[1] << 64 | q[0];
-        const u128h sum = a0 + a1;
-        const uint64_t k1[3] = {(uint64_t)sum, (uint64_t)(sum >> 64), sum < a0 ? 1ull : 0ull};
-        const uint64_t k2[2] = {(uint64_t)a1, (uint64_t)(a1 >> 64)};
-        fph::g1_phi(phis[i], P);
-        put_point(J[0], P);
-        put_point(J[1], phis[i]);
-        put_point(J[2], P);
-        if (!put_digits(J[0], k1, 3, 33) || !put_digits(J[1], k2, 2, 33) || !put_digits(J[2], z2, 2, 33)) return 0;
-        live[i] = 1;
-    }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const void *dj = up(c->mcl[8], (const u32 *)jobs.data(), jobs.size() * sizeof(PtJobG1) / 4, s);
-    void *dout = c->mcl[9].get(3 * n * sizeof(fph::g1));
-    if (!dj || !dout) { set_err("device allocation failed"); return -1; }
-    lcbk_ptmul_g1_multi(s, dj, (u32)(3 * n), dout);
-    std::vector<fph::g1> acc(3 * n);
-    hipMemcpyAsync(acc.data(), dout, 3 * n * sizeof(fph::g1), hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "mulVec")) return -1;
-    fph::g1 r;
-    fph::jac_set_inf(r);
-    for (size_t i = 0; i < n; i++) {
-        if (!live[i]) continue;
-        fph::g1a chk;
-        fph::g1_phi(chk, phis[i]);                // (beta^2 x, y) -> membership: [z^2] P == (beta^2 x, -y)
-        fph::neg(chk.y, chk.y);
-        if (!fph::jac_eq_aff(acc[3 * i + 2], chk)) return 0;
-        fph::g1 t;
-        fph::jac_add(t, acc[3 * i], acc[3 * i + 1]);
-        fph::jac_add(r, r, t);
-    }
-    *G1W(z) = r;
-    return 1;
-}
-// the G2 counterpart: sum_i [k_i] x_i on mclBnG2_mul's GLS ladders (five groups per term, k_ptmul_g2_multi); the
-// same return convention (0: a term off the curve or outside G2 — the caller's exact path)
-static int g2_terms_coop(lcb_ctx *c, mclBnG2 *z, const mclBnG2 *x, const uint64_t (*kraw)[4], size_t n) {
-    std::vector<PtJobG2> jobs(5 * n);
-    memset(jobs.data(), 0, jobs.size() * sizeof(PtJobG2));
-    std::vector<fph::g2a> psis(n);
-    std::vector<uint8_t> live(n, 0);
-    const uint64_t zero[1] = {0};
-    for (size_t i = 0; i < n; i++) {
-        PtJobG2 *J = &jobs[5 * i];
-        const uint64_t *k = kraw[i];
-        fph::g2a Q;
-        fph::jac_to_aff(Q, *G2R(&x[i]));
-        if (!Q.inf && !fph::jac_on_curve(*G2R(&x[i]))) return 0;
-        if (Q.inf || (k[0] | k[1] | k[2] | k[3]) == 0) {
-            for (int j = 0; j < 5; j++) { J[j].inf = 1; put_digits(J[j], zero, 1, 17); }
-            continue;
-        }
-        uint64_t q[4] = {k[0], k[1], k[2], k[3]}, d[4];
-        d[0] = divmod_u(q);
-        d[1] = divmod_u(q);
-        d[2] = divmod_u(q);
-        d[3] = q[0];
-        fph::g2a B[4];
-        B[0] = Q;
-        fph::g2_psi(B[1], Q);
-        fph::g2_psi(B[2], B[1]);
-        fph::g2_psi(B[3], B[2]);
-        psis[i] = B[1];
-        fph::neg(B[1].y, B[1].y);
-        fph::neg(B[3].y, B[3].y);
-        bool ok = true;
-        for (int j = 0; j < 4; j++) {
-            put_point(J[j], B[j]);
-            ok &= put_digits(J[j], &d[j], 1, 17);
-        }
-        put_point(J[4], Q);
-        ok &= put_digits(J[4], &Z_ABS_H, 1, 17);
-        if (!ok) return 0;
-        live[i] = 1;
-    }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const void *dj = up(c->mcl[8], (const u32 *)jobs.data(), jobs.size() * sizeof(PtJobG2) / 4, s);
-    void *dout = c->mcl[9].get(5 * n * sizeof(fph::g2));
-    if (!dj || !dout) { set_err("device allocation failed"); return -1; }
-    lcbk_ptmul_g2_multi(s, dj, (u32)(5 * n), dout);
-    std::vector<fph::g2> acc(5 * n);
-    hipMemcpyAsync(acc.data(), dout, 5 * n * sizeof(fph::g2), hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "G2 terms")) return -1;
-    fph::g2 r;
-    fph::jac_set_inf(r);
-    for (size_t i = 0; i < n; i++) {
-        if (!live[i]) continue;
-        fph::g2a chk = psis[i];                   // membership: psi(Q) == -[|z|] Q
-        fph::neg(chk.y, chk.y);
-        if (!fph::jac_eq_aff(acc[5 * i + 4], chk)) return 0;
-        for (int j = 0; j < 4; j++) fph::jac_add(r, r, acc[5 * i + j]);
-    }
-    *G2W(z) = r;
-    return 1;
-}
-// Lagrange coefficients lambda_i = prod_{j != i} x_j / (x_j - x_i) as canonical raw words; false on a zero or
-// repeated x (the error of k_lagrange_coeffs)
-static bool lagrange_lambdas(std::vector<uint64_t> &raw, const mclBnFr *xVec, size_t k) {
-    raw.assign(4 * k, 0);
-    static const uint64_t one_raw[4] = {1, 0, 0, 0};
-    for (size_t i = 0; i < k; i++) {
-        const uint64_t *xi = FRV(&xVec[i]);
-        if (frh::is_zero(xi)) { set_err("lagrange: zero x"); return false; }
-        uint64_t num[4], den[4], t[4];
-        frh::from_raw(num, one_raw);
-        memcpy(den, num, 32);
-        for (size_t j = 0; j < k; j++) {
-            if (j == i) continue;
-            const uint64_t *xj = FRV(&xVec[j]);
-            frh::sub(t, xj, xi);
-            if (frh::is_zero(t)) { set_err("lagrange: repeated x"); return false; }
-            frh::mul(num, num, xj);
-            frh::mul(den, den, t);
-        }
-        frh::inv(den, den);
-        frh::mul(t, num, den);
-        frh::to_raw(&raw[4 * i], t);
-    }
-    return true;
-}
-// mclBnG1_mulVec: sum_i [y_i] x_i with the canonical scalars (mcl's per-term product, exact for any on-curve x_i):
-// up to MULVEC_COOP_MAX terms on the cooperative ladders above; otherwise (or for a term outside G1) one lane per term
-// (windowed ladder), then block reductions and a one-lane sum
-static bool g1_mulvec(mclBnG1 *z, const mclBnG1 *x, const mclBnFr *y, mclSize n) {
-    SYNC_CTX_OR(c, false)
-    if (n > 0xffffffffu) { set_err("mulVec: too large"); return false; }
-    std::vector<uint64_t> raw(4 * n);
-    for (size_t i = 0; i < n; i++) frh::to_raw(&raw[4 * i], FRV(&y[i]));
-    if (n <= MULVEC_COOP_MAX && g_mulvec_coop) {
-        const int rc = g1_mulvec_coop(c, z, x, (const uint64_t (*)[4])raw.data(), n);
-        if (rc != 0) return rc > 0;
-    }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const u32 *pts = up(c->mcl[0], (const u32 *)x, 36 * n, s);
-    const uint64_t *sc = up(c->mcl[1], raw.data(), 4 * n, s);
-    uint8_t *terms = (uint8_t *)c->mcl[2].get(LCB_G1_JAC_BYTES * n);
-    uint8_t *tmp = (uint8_t *)c->mcl[3].get(LCB_G1_JAC_BYTES * ((n + 255) / 256));
-    uint8_t *dz = (uint8_t *)c->mcl[5].get(LCB_G1_JAC_BYTES);
-    u32 *ws = (u32 *)c->lws.get(lcbk_mcl_terms_ws_bytes((u32)n));
-    if (!pts || !sc || !terms || !tmp || !dz || !ws) { set_err("device allocation failed"); return false; }
-    lcbk_mcl_g1_terms(s, pts, sc, (u32)n, terms, ws);
-    uint8_t *cur = terms;
-    size_t cnt = n;
-    while (cnt > 256) {
-        uint8_t *dst = cur == terms ? tmp : terms;
-        lcbk_g1_jac_reduce_block(s, cur, (u32)cnt, 256, dst);
-        cnt = (cnt + 255) / 256;
-        cur = dst;
-    }
-    lcbk_mcl_g1_sum(s, cur, (u32)cnt, dz);
-    mclBnG1 r;
-    hipMemcpyAsync(&r, dz, 144, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "mulVec")) return false;
-    *z = r;
-    return true;
-}
-extern "C" void mclBnG1_mulVec(mclBnG1 *z, const mclBnG1 *x, const mclBnFr *y, mclSize n) {
-    if (n == 0) { mclBnG1_clear(z); return; }
-    if (!g1_mulvec(z, x, y, n)) fail_out(z, 144);
-}
-// G1 / G2 Lagrange interpolation of one problem on the batch kernels: mcl records -> wire bytes on the device, the
-// k_lagrange.hip coefficient + product kernels, the result decoded back into an mcl record (one round trip)
-static int lagrange_points(int g, void *out, const mclBnFr *xVec, const void *yVec, mclSize k) {
-    if (k == 0) return -1;
-    SYNC_CTX_OR(c, -1)
-    if (k > 0xffffffffu) { set_err("lagrange: too large"); return -1; }
-    const size_t pb = g == 1 ? 48 : 96, words = g == 1 ? 36 : 72;
-    std::vector<uint64_t> xs(4 * k);
-    for (size_t i = 0; i < k; i++) frh::to_raw(&xs[4 * i], FRV(&xVec[i]));
-    const uint32_t off[2] = {0, (uint32_t)k};
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const uint8_t *dx = (const uint8_t *)up(c->mcl[0], xs.data(), 4 * k, s);
-    const u32 *dyr = up(c->mcl[1], (const u32 *)yVec, words * k, s);
-    const uint32_t *doff = up(c->mcl[2], off, 2, s);
-    uint8_t *dy = (uint8_t *)c->mcl[3].get(pb * k);
-    uint8_t *dst = (uint8_t *)c->mcl[4].get(16), *dout = (uint8_t *)c->mcl[5].get(pb);
-    u32 *rec = (u32 *)c->mcl[6].get(words * 4);
-    uint8_t *dok = (uint8_t *)c->mcl[7].get(16);
-    if (!dx || !dyr || !doff || !dy || !dst || !dout || !rec || !dok) { set_err("device allocation failed"); return -1; }
-    lcbk_mcl_to_bytes(s, g, dyr, (u32)k, dy);
-    if (lagrange_enqueue(c, g, dout, dst, dx, dy, doff, 1, k, s)) return -1;
-    lcbk_mcl_from_bytes(s, g, dout, 1, rec, dok);
-    u32 r[72];
-    uint8_t st = 0, ok = 0;
-    hipMemcpyAsync(r, rec, words * 4, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(&st, dst, 1, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(&ok, dok, 1, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "lagrange") || !st || !ok) return -1;
-    memcpy(out, r, words * 4);
-    return 0;
-}
-// G1 Lagrange interpolation of up to 64 points: the coefficients lambda_i = prod_{j != i} x_j / (x_j - x_i) on the host
-// (-1 on a zero or repeated x, as k_lagrange_coeffs), the products on the cooperative ladders (g1_mulvec_coop); 1 done,
-// 0 for the batch kernels' path (a point outside G1, or more points)
-static int g1_lagrange_coop(mclBnG1 *out, const mclBnFr *xVec, const mclBnG1 *yVec, size_t k) {
-    if (k > 64 || !g_mulvec_coop) return 0;
-    SYNC_CTX_OR(c, -1)
-    std::vector<uint64_t> raw;
-    if (!lagrange_lambdas(raw, xVec, k)) return -1;
-    const int rc = g1_mulvec_coop(c, out, yVec, (const uint64_t (*)[4])raw.data(), k);
-    return rc < 0 ? -1 : rc;
-}
-// the same in G2 (AssembleSignature's interpolation, ThresholdSignature/PublicKeySet.cs:34-42)
-static int g2_lagrange_coop(mclBnG2 *out, const mclBnFr *xVec, const mclBnG2 *yVec, size_t k) {
-    if (k > 64 || !g_mulvec_coop) return 0;
-    SYNC_CTX_OR(c, -1)
-    std::vector<uint64_t> raw;
-    if (!lagrange_lambdas(raw, xVec, k)) return -1;
-    const int rc = g2_terms_coop(c, out, yVec, (const uint64_t (*)[4])raw.data(), k);
-    return rc < 0 ? -1 : rc;
-}
-extern "C" int mclBn_G1LagrangeInterpolation(mclBnG1 *out, const mclBnFr *xVec, const mclBnG1 *yVec, mclSize k) {
-    if (k == 1) { *out = yVec[0]; return mclBnFr_isZero(&xVec[0]) ? -1 : 0; }
-    if (k == 0) return -1;
-    const int rc = g1_lagrange_coop(out, xVec, yVec, k);
-    if (rc != 0) return rc > 0 ? 0 : -1;
-    return lagrange_points(1, out, xVec, yVec, k);
-}
-extern "C" int mclBn_G2LagrangeInterpolation(mclBnG2 *out, const mclBnFr *xVec, const mclBnG2 *yVec, mclSize k) {
-    if (k == 1) { *out = yVec[0]; return mclBnFr_isZero(&xVec[0]) ? -1 : 0; }
-    if (k == 0) return -1;
-    const int rc = g2_lagrange_coop(out, xVec, yVec, k);
-    if (rc != 0) return rc > 0 ? 0 : -1;
-    return lagrange_points(2, out, xVec, yVec, k);
-}
-// out = a x mod #E(Fp) for G1 (a < #E, x < 2^256): #E(Fp) = p - z = h r (z = -0xd201000000010000), so [k] P depends
-// only on k mod #E for every point P of E(Fp), in the subgroup or not
-static void ne_mulmod(uint64_t out[6], const uint64_t a[6], const uint64_t x[4]) {
-    static const uint64_t NE[6] = {0x8c0000000000aaabull, 0x1eabfffeb1540000ull, 0x6730d2a0f6b0f624ull,
-                                   0x64774b84f38512bfull, 0x4b1ba7b6434bacd7ull, 0x1a0111ea397fe69aull};
-    typedef unsigned __int128 u128;
-    uint64_t prod[10] = {0};
-    for (int i = 0; i < 6; i++) {
-        uint64_t carry = 0;
-        for (int j = 0; j < 4; j++) {
-            const u128 t = (u128)a[i] * x[j] + prod[i + j] + carry;
-            prod[i + j] = (uint64_t)t;
-            carry = (uint64_t)(t >> 64);
-        }
-        prod[i + 4] = carry;
-    }
-    uint64_t rem[6] = {0};                       // long division by bits: rem < NE < 2^381, so 2 rem + 1 fits
-    for (int b = 639; b >= 0; b--) {
-        for (int k = 5; k > 0; k--) rem[k] = (rem[k] << 1) | (rem[k - 1] >> 63);
-        rem[0] = (rem[0] << 1) | ((prod[b >> 6] >> (b & 63)) & 1);
-        int ge = 1;
-        for (int k = 5; k >= 0; k--) {
-            if (rem[k] != NE[k]) { ge = rem[k] > NE[k]; break; }
-        }
-        if (ge) {
-            uint64_t br = 0;
-            for (int k = 0; k < 6; k++) {
-                const u128 t = (u128)rem[k] - NE[k] - br;
-                rem[k] = (uint64_t)t;
-                br = (uint64_t)(t >> 64) & 1;
-            }
-        }
-    }
-    memcpy(out, rem, 48);
-}
-// G1 EvaluatePolynomial as a sum of independent terms: sum_i [x^i mod #E] c_i (k_mcl_g1_terms_wide, one lane per term,
-// then the mulVec sums) — the value of mcl's Horner rule for every on-curve coefficient, with the products side by
-// side instead of n - 1 dependent ones
-static int eval_poly_g1_terms(lcb_ctx *c, mclBnG1 *out, const mclBnG1 *coef, size_t n, const uint64_t xr[4]) {
-    std::vector<uint32_t> sc(12 * n);
-    uint64_t e[6] = {1, 0, 0, 0, 0, 0};
-    for (size_t i = 0; i < n; i++) {
-        if (i) ne_mulmod(e, e, xr);
-        memcpy(&sc[12 * i], e, 48);
-    }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const u32 *pts = up(c->mcl[0], (const u32 *)coef, 36 * n, s);
-    const u32 *dsc = up(c->mcl[1], sc.data(), 12 * n, s);
-    uint8_t *terms = (uint8_t *)c->mcl[2].get(LCB_G1_JAC_BYTES * n);
-    uint8_t *tmp = (uint8_t *)c->mcl[3].get(LCB_G1_JAC_BYTES * ((n + 255) / 256));
-    uint8_t *dz = (uint8_t *)c->mcl[5].get(LCB_G1_JAC_BYTES);
-    u32 *ws = (u32 *)c->lws.get(lcbk_mcl_terms_wide_ws_bytes((u32)n));
-    if (!pts || !dsc || !terms || !tmp || !dz || !ws) { set_err("device allocation failed"); return -1; }
-    lcbk_mcl_g1_terms_wide(s, pts, dsc, (u32)n, terms, ws);
-    uint8_t *cur = terms;
-    size_t cnt = n;
-    while (cnt > 256) {
-        uint8_t *dst = cur == terms ? tmp : terms;
-        lcbk_g1_jac_reduce_block(s, cur, (u32)cnt, 256, dst);
-        cnt = (cnt + 255) / 256;
-        cur = dst;
-    }
-    lcbk_mcl_g1_sum(s, cur, (u32)cnt, dz);
-    mclBnG1 r;
-    hipMemcpyAsync(&r, dz, 144, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "evaluate polynomial")) return -1;
-    *out = r;
-    return 0;
-}
-// G1 / G2 EvaluatePolynomial: mcl's Horner rule (y = c[n-1]; y = y x + c[i]) — the products are by the integer x, as
-// mcl's, so off-subgroup coefficients give mcl's value too.  G1 (n >= 2): the same value as independent terms (above);
-// G2 and LCB_EVAL_HORNER=1: the Horner chain in one kernel launch
-static int eval_poly(int g, void *out, const void *coef, mclSize n, const mclBnFr *x) {
-    if (n == 0) return -1;
-    SYNC_CTX_OR(c, -1)
-    if (n > 0xffffffffu) { set_err("evaluate polynomial: too large"); return -1; }
-    const size_t words = g == 1 ? 36 : 72;
-    uint64_t xr[4];
-    frh::to_raw(xr, FRV(x));
-    static const bool horner = getenv("LCB_EVAL_HORNER") && atoi(getenv("LCB_EVAL_HORNER")) == 1;
-    if (g == 1 && n >= 2 && n <= MULVEC_COOP_MAX && !horner && g_mulvec_coop) {
-        // coefficients in G1: [x^i mod r] c_i on the cooperative ladders (a coefficient outside G1 returns 0 here
-        // and takes the terms below, whose powers are reduced mod #E(Fp) instead)
-        std::vector<uint64_t> raw(4 * n);
-        uint64_t pw[4], one_raw[4] = {1, 0, 0, 0};
-        frh::from_raw(pw, one_raw);
-        for (size_t i = 0; i < n; i++) {
-            frh::to_raw(&raw[4 * i], pw);
-            frh::mul(pw, pw, FRV(x));
-        }
-        const int rc = g1_mulvec_coop(c, (mclBnG1 *)out, (const mclBnG1 *)coef, (const uint64_t (*)[4])raw.data(), n);
-        if (rc != 0) return rc > 0 ? 0 : -1;
-    }
-    if (g == 1 && n >= 2 && !horner) return eval_poly_g1_terms(c, (mclBnG1 *)out, (const mclBnG1 *)coef, n, xr);
-    if (g == 2 && n >= 2 && n <= 64 && !horner && g_mulvec_coop) {   // coefficients in G2: [x^i mod r] c_i, GLS
-        std::vector<uint64_t> raw(4 * n);
-        uint64_t pw[4], one_raw[4] = {1, 0, 0, 0};
-        frh::from_raw(pw, one_raw);
-        for (size_t i = 0; i < n; i++) {
-            frh::to_raw(&raw[4 * i], pw);
-            frh::mul(pw, pw, FRV(x));
-        }
-        const int rc = g2_terms_coop(c, (mclBnG2 *)out, (const mclBnG2 *)coef, (const uint64_t (*)[4])raw.data(), n);
-        if (rc != 0) return rc > 0 ? 0 : -1;
-    }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const u32 *dc = up(c->mcl[0], (const u32 *)coef, words * n, s);
-    const uint64_t *dx = up(c->mcl[1], xr, 4, s);
-    u32 *dout = (u32 *)c->mcl[2].get(words * 4);
-    if (!dc || !dx || !dout) { set_err("device allocation failed"); return -1; }
-    lcbk_mcl_horner(s, g, dc, (u32)n, dx, dout);
-    u32 r[72];
-    hipMemcpyAsync(r, dout, words * 4, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "evaluate polynomial")) return -1;
-    memcpy(out, r, words * 4);
-    return 0;
-}
-extern "C" int mclBn_G1EvaluatePolynomial(mclBnG1 *out, const mclBnG1 *c, mclSize n, const mclBnFr *x) {
-    return eval_poly(1, out, c, n, x);
-}
-extern "C" int mclBn_G2EvaluatePolynomial(mclBnG2 *out, const mclBnG2 *c, mclSize n, const mclBnFr *x) {
-    return eval_poly(2, out, c, n, x);
-}
 
 static int mul_batch(int g, uint8_t *out, const uint8_t *points, int use_gen, const uint8_t *scalars, size_t n) {
     SYNC_CTX_OR(c, -1)
@@ -3064,7 +1560,7 @@ extern "C" int lcb_g1_to_affine_dev(void *out_aff, uint8_t *ok, const uint8_t *p
     if (!ready()) return -1;
     if (n > 0xffffffffu) { set_err("to_affine: batch too large"); return -1; }
     if (n) lcbk_g1_to_affine(dim3(nblk(n)), (hipStream_t)stream, points, (u32)n, out_aff, ok);
-    return launched("to_affine launch") ? 0 : -1;
+    return launch_ok("to_affine launch") ? 0 : -1;
 }
 extern "C" int lcb_ctx_g1_jac_sum_dev(lcb_ctx *ctx, uint8_t *out48, void *out_jac, const void *parts, size_t k,
                                       void *stream) {
@@ -3072,16 +1568,24 @@ extern "C" int lcb_ctx_g1_jac_sum_dev(lcb_ctx *ctx, uint8_t *out48, void *out_ja
     Enq q(c, (hipStream_t)stream);
     if (k == 1 && !out_jac && out48) {          // one partial (a single rank): serialise it as it is
         lcbk_g1_jac_compress(dim3(1), q.s, parts, 1, out48);
-        return launched("jac sum launch") ? 0 : -1;
+        return launch_ok("jac sum launch") ? 0 : -1;
     }
     void *acc = out_jac ? out_jac : c->msm[14].get(LCB_G1_JAC_BYTES);
     if (!acc) { set_err("device allocation failed"); return -1; }
     lcbk_g1_jac_reduce_groups(dim3(1), q.s, parts, (u32)k, k ? (u32)k : 1u, acc);
     if (out48) lcbk_g1_jac_compress(dim3(1), q.s, acc, 1, out48);
-    return launched("jac sum launch") ? 0 : -1;
+    return launch_ok("jac sum launch") ? 0 : -1;
 }
 extern "C" int lcb_g1_jac_sum_dev(uint8_t *out48, void *out_jac, const void *parts, size_t k, void *stream) {
     return lcb_ctx_g1_jac_sum_dev(nullptr, out48, out_jac, parts, k, stream);
+}
+// canonical Fr bytes (32-byte LE < r)
+static bool fr_bytes_lt_r(const uint8_t *b) {
+    for (int j = 7; j >= 0; j--) {
+        uint32_t w = (uint32_t)b[4 * j] | (uint32_t)b[4 * j + 1] << 8 | (uint32_t)b[4 * j + 2] << 16 | (uint32_t)b[4 * j + 3] << 24;
+        if (w != LCB_R_HOST[j]) return w < LCB_R_HOST[j];
+    }
+    return false;
 }
 extern "C" int lcb_g1_msm(uint8_t out[48], const uint8_t *points, const uint8_t *scalars, size_t n) {
     SYNC_CTX_OR(c, -1)
@@ -3113,13 +1617,3 @@ extern "C" int lcb_g1_msm(uint8_t out[48], const uint8_t *points, const uint8_t 
 extern "C" void lcb_xor_with_hash(uint8_t *out, const uint8_t g1b[48], const uint8_t *data, size_t len) {
     lcb_host::xor_with_hash(out, g1b, data, len);
 }
-
-// ================================================================== internal interface for the other host files
-namespace lcb_int {
-void set_error(const char *what, hipError_t e) { set_err(what, e); }
-lcb_ctx *ctx_resolve(lcb_ctx *c) { return resolve(c); }
-lcb_ctx *ctx_sync() { return sync_ctx(); }
-bool launch_ok(const char *what) { return launched(what); }
-bool sync_ok(lcb_ctx *c, const char *what) { return sync_check(c, what); }
-int device() { return g_device; }
-}  // namespace lcb_int

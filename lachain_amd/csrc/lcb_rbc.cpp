@@ -1,5 +1,6 @@
-// lachain_amd/csrc/lcb_rbc.cpp — host side of the reliable broadcast's Merkle layer and the block transaction root
-// (include/lachain_bls.h "reliable broadcast: Merkle layer").
+// lachain_amd/csrc/lcb_rbc.cpp — host side of the reliable broadcast's Merkle layer, the block transaction root
+// (include/lachain_bls.h "reliable broadcast: Merkle layer") and, at the end, the single-instance
+// Reed-Solomon encode / decode (lcb_rs_*) on the same k_rs.hip kernels.
 //
 // Reference calls: ReliableBroadcast.HandleInputMessage -> AugmentInput + ConstructValMessages (ReliableBroadcast.cs:
 // 116, 311-338), CheckEchoMessage (:173, :296-309), TrySendReadyMessageFromEchos (:201-234: DecodeFromEchos, rebuild the
@@ -22,7 +23,7 @@ const size_t MAX_BATCH = 65535;          // instances per call: the grid's y dim
 const size_t MAX_ITEMS = 0x7fffffffu;
 
 bool shards_ok(int n, const char *what) {
-    if (n < 1 || n > 256) { set_error(what); return false; }
+    if (n < 1 || n > 256) { set_err(what); return false; }
     return true;
 }
 int depth_of(int n) {
@@ -32,7 +33,7 @@ int depth_of(int n) {
 }
 bool monotone(const uint64_t *off, size_t n, const char *what) {
     for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) { set_error(what); return false; }
+        if (off[i + 1] < off[i]) { set_err(what); return false; }
     return true;
 }
 void rs_matrix_lds() {
@@ -42,18 +43,13 @@ void rs_matrix_lds() {
     (void)hipFuncSetAttribute(lcbk_rs_matrix_batch_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, 65536 * 2);
     attr = true;
 }
-template <class T> T *upload(DevBuf &b, const T *src, size_t count, hipStream_t s) {
-    T *d = (T *)b.get(count * sizeof(T));
-    if (d && count) hipMemcpyAsync(d, src, count * sizeof(T), hipMemcpyHostToDevice, s);
-    return d;
-}
 
 }  // namespace
 
 // ------------------------------------------------------------------ sizes (host arithmetic, no device)
 extern "C" size_t lcb_rbc_shard_size(size_t payload_len, int n, int f) {
     if (n < 1 || n > 256 || f < 0 || n - 2 * f <= 0 || payload_len > 0x7fffffffu - 4) {
-        set_error("rbc shard size: need 1 <= n <= 256, 0 <= 2f < n and a payload below 2^31 - 4 bytes");
+        set_err("rbc shard size: need 1 <= n <= 256, 0 <= 2f < n and a payload below 2^31 - 4 bytes");
         return 0;
     }
     size_t k = (size_t)(n - 2 * f);
@@ -69,9 +65,9 @@ extern "C" int lcb_rbc_val_batch(uint8_t *shards_out, uint8_t *roots_out, uint8_
                                  const uint64_t *payload_off, size_t B, int n, int f) {
     lcb_ctx *c = ctx_sync();
     if (!c) return -1;
-    if (n < 1 || n > 256 || f < 0 || n - 2 * f <= 0) { set_error("rbc val: need 1 <= n <= 256 and 0 <= 2f < n"); return -1; }
+    if (n < 1 || n > 256 || f < 0 || n - 2 * f <= 0) { set_err("rbc val: need 1 <= n <= 256 and 0 <= 2f < n"); return -1; }
     if (!B) return 0;
-    if (B > MAX_BATCH) { set_error("rbc val: at most 65535 instances per call"); return -1; }
+    if (B > MAX_BATCH) { set_err("rbc val: at most 65535 instances per call"); return -1; }
     if (!monotone(payload_off, B, "rbc val: offsets must not decrease")) return -1;
     const int k = n - 2 * f, m = 2 * f, depth = depth_of(n);
     std::vector<uint64_t> poff(B + 1), soff(B + 1);
@@ -79,7 +75,7 @@ extern "C" int lcb_rbc_val_batch(uint8_t *shards_out, uint8_t *roots_out, uint8_
     soff[0] = 0;
     for (size_t b = 0; b < B; b++) {
         uint64_t len = payload_off[b + 1] - payload_off[b];
-        if (len > 0x7fffffffu - 4) { set_error("rbc val: payload too long for the int32 length prefix"); return -1; }
+        if (len > 0x7fffffffu - 4) { set_err("rbc val: payload too long for the int32 length prefix"); return -1; }
         size_t S = (size_t)((len + 4 + k - 1) / k);
         max_S = S > max_S ? S : max_S;
         soff[b + 1] = soff[b] + (uint64_t)n * S;
@@ -87,16 +83,16 @@ extern "C" int lcb_rbc_val_batch(uint8_t *shards_out, uint8_t *roots_out, uint8_
     for (size_t b = 0; b <= B; b++) poff[b] = payload_off[b] - payload_off[0];
     Enq q(c, c->stream);
     hipStream_t s = c->stream;
-    const uint8_t *dpay = upload(c->rbc[0], payloads + payload_off[0], (size_t)poff[B], s);
-    const uint64_t *dpoff = upload(c->rbc[1], poff.data(), B + 1, s);
-    const uint64_t *dsoff = upload(c->rbc[2], soff.data(), B + 1, s);
+    const uint8_t *dpay = up(c->rbc[0], payloads + payload_off[0], (size_t)poff[B], s);
+    const uint64_t *dpoff = up(c->rbc[1], poff.data(), B + 1, s);
+    const uint64_t *dsoff = up(c->rbc[2], soff.data(), B + 1, s);
     uint8_t *dsh = (uint8_t *)c->rbc[3].get((size_t)soff[B]);
     int *dpos = (int *)c->rbc[4].get(4 * (size_t)n);
     uint8_t *dM = (uint8_t *)c->rbc[5].get((size_t)m * k + 16);
     uint8_t *droots = (uint8_t *)c->rbc[7].get(32 * B);
     uint8_t *dproofs = (uint8_t *)c->rbc[8].get(32 * B * n * (size_t)depth);
     if (!dpay || !dpoff || !dsoff || !dsh || !dpos || !dM || !droots || !dproofs) {
-        set_error("device allocation failed");
+        set_err("device allocation failed");
         return -1;
     }
     lcbk_rbc_augment(s, dpay, dpoff, dsh, dsoff, n, k, max_S * k, (unsigned)B);
@@ -117,8 +113,8 @@ extern "C" int lcb_rbc_val_batch(uint8_t *shards_out, uint8_t *roots_out, uint8_
     if (shards_out) hipMemcpyAsync(shards_out, dsh, (size_t)soff[B], hipMemcpyDeviceToHost, s);
     if (roots_out) hipMemcpyAsync(roots_out, droots, 32 * B, hipMemcpyDeviceToHost, s);
     if (proofs_out && depth) hipMemcpyAsync(proofs_out, dproofs, 32 * B * n * (size_t)depth, hipMemcpyDeviceToHost, s);
-    if (!sync_ok(c, "rbc val")) return -1;
-    if (!ok) { set_error("rbc val: parity positions are not independent"); return -1; }
+    if (!sync_check(c, "rbc val")) return -1;
+    if (!ok) { set_err("rbc val: parity positions are not independent"); return -1; }
     return 0;
 }
 
@@ -129,7 +125,7 @@ extern "C" int lcb_ctx_rbc_check_echo_dev(lcb_ctx *ctx, uint8_t *accept, const u
     lcb_ctx *c = ctx_resolve(ctx);
     if (!c) return -1;
     if (!shards_ok(n_shards, "rbc check echo: need 1 <= n_shards <= 256")) return -1;
-    if (n_items > MAX_ITEMS) { set_error("rbc check echo: batch too large"); return -1; }
+    if (n_items > MAX_ITEMS) { set_err("rbc check echo: batch too large"); return -1; }
     Enq q(c, (hipStream_t)stream);
     if (!n_items) return 0;
     lcbk_rbc_echo(q.s, accept, data, data_off, from, roots, proofs, proof_off, (u32)n_items, n_shards);
@@ -148,7 +144,7 @@ extern "C" int lcb_rbc_check_echo_batch(uint8_t *accept, const uint8_t *data, co
     if (!c) return -1;
     if (!shards_ok(n_shards, "rbc check echo: need 1 <= n_shards <= 256")) return -1;
     if (!n_items) return 0;
-    if (n_items > MAX_ITEMS) { set_error("rbc check echo: batch too large"); return -1; }
+    if (n_items > MAX_ITEMS) { set_err("rbc check echo: batch too large"); return -1; }
     if (!monotone(data_off, n_items, "rbc check echo: data offsets must not decrease") ||
         !monotone(proof_off, n_items, "rbc check echo: proof offsets must not decrease"))
         return -1;
@@ -156,17 +152,17 @@ extern "C" int lcb_rbc_check_echo_batch(uint8_t *accept, const uint8_t *data, co
     for (size_t i = 0; i <= n_items; i++) { doff[i] = data_off[i] - data_off[0]; poff[i] = proof_off[i] - proof_off[0]; }
     Enq q(c, c->stream);
     hipStream_t s = c->stream;
-    const uint8_t *dd = upload(c->rbc[0], data + data_off[0], (size_t)doff[n_items], s);
-    const uint64_t *ddoff = upload(c->rbc[1], doff.data(), n_items + 1, s);
-    const uint64_t *dpoff = upload(c->rbc[2], poff.data(), n_items + 1, s);
-    const int32_t *dfrom = upload(c->rbc[4], from, n_items, s);
-    const uint8_t *dpr = upload(c->rbc[10], proofs + 32 * proof_off[0], 32 * (size_t)poff[n_items], s);
-    const uint8_t *droots = upload(c->rbc[11], roots, 32 * n_items, s);
+    const uint8_t *dd = up(c->rbc[0], data + data_off[0], (size_t)doff[n_items], s);
+    const uint64_t *ddoff = up(c->rbc[1], doff.data(), n_items + 1, s);
+    const uint64_t *dpoff = up(c->rbc[2], poff.data(), n_items + 1, s);
+    const int32_t *dfrom = up(c->rbc[4], from, n_items, s);
+    const uint8_t *dpr = up(c->rbc[10], proofs + 32 * proof_off[0], 32 * (size_t)poff[n_items], s);
+    const uint8_t *droots = up(c->rbc[11], roots, 32 * n_items, s);
     uint8_t *dacc = (uint8_t *)c->rbc[9].get(n_items);
-    if (!dd || !ddoff || !dpoff || !dfrom || !dpr || !droots || !dacc) { set_error("device allocation failed"); return -1; }
+    if (!dd || !ddoff || !dpoff || !dfrom || !dpr || !droots || !dacc) { set_err("device allocation failed"); return -1; }
     if (lcb_ctx_rbc_check_echo_dev(c, dacc, dd, ddoff, dfrom, droots, dpr, dpoff, n_items, n_shards, s)) return -1;
     hipMemcpyAsync(accept, dacc, n_items, hipMemcpyDeviceToHost, s);
-    return sync_ok(c, "rbc check echo") ? 0 : -1;
+    return sync_check(c, "rbc check echo") ? 0 : -1;
 }
 
 // ------------------------------------------------------------------ ConstructMerkleTree
@@ -175,8 +171,8 @@ extern "C" int lcb_ctx_rbc_merkle_tree_dev(lcb_ctx *ctx, uint8_t *trees_out, con
     lcb_ctx *c = ctx_resolve(ctx);
     if (!c) return -1;
     if (!shards_ok(n_shards, "rbc merkle tree: need 1 <= n_shards <= 256")) return -1;
-    if (B > MAX_ITEMS) { set_error("rbc merkle tree: batch too large"); return -1; }
-    if (((uintptr_t)trees_out) & 7) { set_error("rbc merkle tree: trees_out must be 8-byte aligned"); return -1; }
+    if (B > MAX_ITEMS) { set_err("rbc merkle tree: batch too large"); return -1; }
+    if (((uintptr_t)trees_out) & 7) { set_err("rbc merkle tree: trees_out must be 8-byte aligned"); return -1; }
     Enq q(c, (hipStream_t)stream);
     if (!B) return 0;
     lcbk_rbc_tree(q.s, shards, shard_off, n_shards, depth_of(n_shards), trees_out, nullptr, nullptr, (unsigned)B);
@@ -192,25 +188,25 @@ extern "C" int lcb_rbc_merkle_tree_batch(uint8_t *trees_out, const uint8_t *shar
     if (!c) return -1;
     if (!shards_ok(n_shards, "rbc merkle tree: need 1 <= n_shards <= 256")) return -1;
     if (!B) return 0;
-    if (B > MAX_ITEMS) { set_error("rbc merkle tree: batch too large"); return -1; }
+    if (B > MAX_ITEMS) { set_err("rbc merkle tree: batch too large"); return -1; }
     if (!monotone(shard_off, B, "rbc merkle tree: offsets must not decrease")) return -1;
     std::vector<uint64_t> off(B + 1);
     for (size_t b = 0; b <= B; b++) off[b] = shard_off[b] - shard_off[0];
     for (size_t b = 0; b < B; b++)
         if ((off[b + 1] - off[b]) % (uint64_t)n_shards) {
-            set_error("rbc merkle tree: an instance's bytes are not n_shards equal shards");
+            set_err("rbc merkle tree: an instance's bytes are not n_shards equal shards");
             return -1;
         }
     const size_t tree_bytes = 64 * ((size_t)1 << depth_of(n_shards));
     Enq q(c, c->stream);
     hipStream_t s = c->stream;
-    const uint8_t *dsh = upload(c->rbc[0], shards + shard_off[0], (size_t)off[B], s);
-    const uint64_t *doff = upload(c->rbc[1], off.data(), B + 1, s);
+    const uint8_t *dsh = up(c->rbc[0], shards + shard_off[0], (size_t)off[B], s);
+    const uint64_t *doff = up(c->rbc[1], off.data(), B + 1, s);
     uint8_t *dtrees = (uint8_t *)c->rbc[8].get(tree_bytes * B);
-    if (!dsh || !doff || !dtrees) { set_error("device allocation failed"); return -1; }
+    if (!dsh || !doff || !dtrees) { set_err("device allocation failed"); return -1; }
     if (lcb_ctx_rbc_merkle_tree_dev(c, dtrees, dsh, doff, B, n_shards, s)) return -1;
     hipMemcpyAsync(trees_out, dtrees, tree_bytes * B, hipMemcpyDeviceToHost, s);
-    return sync_ok(c, "rbc merkle tree") ? 0 : -1;
+    return sync_check(c, "rbc merkle tree") ? 0 : -1;
 }
 
 // ------------------------------------------------------------------ TrySendReadyMessageFromEchos
@@ -219,10 +215,10 @@ extern "C" int lcb_rbc_decode_batch(uint8_t *shards_out, uint8_t *status, uint8_
                                     const uint8_t *expected_roots, size_t B, int n, int f) {
     lcb_ctx *c = ctx_sync();
     if (!c) return -1;
-    if (n < 1 || n > 256 || f < 0 || n - 2 * f <= 0) { set_error("rbc decode: need 1 <= n <= 256 and 0 <= 2f < n"); return -1; }
+    if (n < 1 || n > 256 || f < 0 || n - 2 * f <= 0) { set_err("rbc decode: need 1 <= n <= 256 and 0 <= 2f < n"); return -1; }
     if (!B) return 0;
-    if (B > MAX_BATCH) { set_error("rbc decode: at most 65535 instances per call"); return -1; }
-    if (!status) { set_error("rbc decode: status is required"); return -1; }
+    if (B > MAX_BATCH) { set_err("rbc decode: at most 65535 instances per call"); return -1; }
+    if (!status) { set_err("rbc decode: status is required"); return -1; }
     if (!monotone(echo_off, B, "rbc decode: offsets must not decrease")) return -1;
     const int k = n - 2 * f, m = 2 * f, depth = depth_of(n);
     std::vector<uint64_t> eoff(B + 1), soff(B + 1);
@@ -231,7 +227,7 @@ extern "C" int lcb_rbc_decode_batch(uint8_t *shards_out, uint8_t *status, uint8_
     for (size_t b = 0; b <= B; b++) eoff[b] = echo_off[b] - echo_off[0];
     for (size_t b = 0; b < B; b++) {
         uint64_t bytes = eoff[b + 1] - eoff[b];
-        if (bytes % (uint64_t)k) { set_error("rbc decode: an instance's bytes are not n - 2f equal echoes"); return -1; }
+        if (bytes % (uint64_t)k) { set_err("rbc decode: an instance's bytes are not n - 2f equal echoes"); return -1; }
         size_t S = (size_t)(bytes / k);
         max_S = S > max_S ? S : max_S;
         soff[b + 1] = soff[b] + (uint64_t)n * S;
@@ -258,16 +254,16 @@ extern "C" int lcb_rbc_decode_batch(uint8_t *shards_out, uint8_t *status, uint8_
     Enq q(c, c->stream);
     hipStream_t s = c->stream;
     rs_matrix_lds();
-    const uint8_t *decho = upload(c->rbc[0], echo_data + echo_off[0], (size_t)eoff[B], s);
-    const uint64_t *deoff = upload(c->rbc[1], eoff.data(), B + 1, s);
-    const uint64_t *dsoff = upload(c->rbc[2], soff.data(), B + 1, s);
+    const uint8_t *decho = up(c->rbc[0], echo_data + echo_off[0], (size_t)eoff[B], s);
+    const uint64_t *deoff = up(c->rbc[1], eoff.data(), B + 1, s);
+    const uint64_t *dsoff = up(c->rbc[2], soff.data(), B + 1, s);
     uint8_t *dsh = (uint8_t *)c->rbc[3].get((size_t)soff[B]);
-    const int *dpos = upload(c->rbc[4], pos.data(), pos.size(), s);
+    const int *dpos = up(c->rbc[4], pos.data(), pos.size(), s);
     uint8_t *dM = (uint8_t *)c->rbc[5].get(B * (size_t)m * k + B);
-    const uint8_t *dvalid = upload(c->rbc[6], valid.data(), B, s);
+    const uint8_t *dvalid = up(c->rbc[6], valid.data(), B, s);
     uint8_t *droots = (uint8_t *)c->rbc[7].get(32 * B);
     if (!decho || !deoff || !dsoff || !dsh || !dpos || !dM || !dvalid || !droots) {
-        set_error("device allocation failed");
+        set_err("device allocation failed");
         return -1;
     }
     uint8_t *dok = dM + B * (size_t)m * k;
@@ -280,7 +276,7 @@ extern "C" int lcb_rbc_decode_batch(uint8_t *shards_out, uint8_t *status, uint8_
     if (shards_out) hipMemcpyAsync(shards_out, dsh, (size_t)soff[B], hipMemcpyDeviceToHost, s);
     hipMemcpyAsync(status, dok, B, hipMemcpyDeviceToHost, s);
     hipMemcpyAsync(roots.data(), droots, 32 * B, hipMemcpyDeviceToHost, s);
-    if (!sync_ok(c, "rbc decode")) return -1;
+    if (!sync_check(c, "rbc decode")) return -1;
     for (size_t b = 0; b < B; b++) {
         status[b] = status[b] ? 1 : 0;
         if (!status[b]) memset(&roots[32 * b], 0, 32);
@@ -295,11 +291,11 @@ extern "C" int lcb_ctx_merkle_root_dev(lcb_ctx *ctx, uint8_t *roots_out, uint8_t
                                        const uint64_t *off, size_t n_trees, size_t n_hashes, void *stream) {
     lcb_ctx *c = ctx_resolve(ctx);
     if (!c) return -1;
-    if (n_trees > MAX_ITEMS) { set_error("merkle root: batch too large"); return -1; }
+    if (n_trees > MAX_ITEMS) { set_err("merkle root: batch too large"); return -1; }
     Enq q(c, (hipStream_t)stream);
     if (!n_trees) return 0;
     uint8_t *ws = (uint8_t *)c->rbc[8].get(32 * n_hashes);
-    if (!ws) { set_error("device allocation failed"); return -1; }
+    if (!ws) { set_err("device allocation failed"); return -1; }
     lcbk_merkle_root(q.s, roots_out, status, hashes, off, ws, (unsigned)n_trees);
     return launch_ok("merkle root launch") ? 0 : -1;
 }
@@ -312,18 +308,103 @@ extern "C" int lcb_merkle_root_batch(uint8_t *roots_out, uint8_t *status, const 
     lcb_ctx *c = ctx_sync();
     if (!c) return -1;
     if (!n_trees) return 0;
-    if (n_trees > MAX_ITEMS) { set_error("merkle root: batch too large"); return -1; }
+    if (n_trees > MAX_ITEMS) { set_err("merkle root: batch too large"); return -1; }
     if (!monotone(off, n_trees, "merkle root: offsets must not decrease")) return -1;
     std::vector<uint64_t> rel(n_trees + 1);
     for (size_t t = 0; t <= n_trees; t++) rel[t] = off[t] - off[0];
     Enq q(c, c->stream);
     hipStream_t s = c->stream;
-    const uint8_t *dh = upload(c->rbc[0], hashes + 32 * off[0], 32 * (size_t)rel[n_trees], s);
-    const uint64_t *doff = upload(c->rbc[1], rel.data(), n_trees + 1, s);
+    const uint8_t *dh = up(c->rbc[0], hashes + 32 * off[0], 32 * (size_t)rel[n_trees], s);
+    const uint64_t *doff = up(c->rbc[1], rel.data(), n_trees + 1, s);
     uint8_t *droots = (uint8_t *)c->rbc[7].get(32 * n_trees), *dst = (uint8_t *)c->rbc[9].get(n_trees);
-    if (!dh || !doff || !droots || !dst) { set_error("device allocation failed"); return -1; }
+    if (!dh || !doff || !droots || !dst) { set_err("device allocation failed"); return -1; }
     if (lcb_ctx_merkle_root_dev(c, droots, dst, dh, doff, n_trees, (size_t)rel[n_trees], s)) return -1;
     hipMemcpyAsync(roots_out, droots, 32 * n_trees, hipMemcpyDeviceToHost, s);
     hipMemcpyAsync(status, dst, n_trees, hipMemcpyDeviceToHost, s);
-    return sync_ok(c, "merkle root") ? 0 : -1;
+    return sync_check(c, "merkle root") ? 0 : -1;
+}
+
+// ================================================================== reliable-broadcast Reed-Solomon (k_rs.hip)
+// ReliableBroadcast.ErasureCodingShards / DecodeFromEchos (src/Lachain.Consensus/ReliableBroadcast/ReliableBroadcast.cs:
+// 393-446): the erased / parity shards are M times the known shards, M = H_E^-1 H_K built on the GPU.  Positions and
+// matrix live in the context's dkg[4] / dkg[5] slots, the shards in in[0] / out[0].
+namespace {
+int rs_enqueue(lcb_ctx *c, uint8_t *d_out, const uint8_t *d_known, const std::vector<int> &pe,
+               const std::vector<int> &pk, int n, size_t S, hipStream_t s, uint8_t **d_ok) {
+    rs_matrix_lds();
+    int m = (int)pe.size(), k = (int)pk.size();
+    int *dpe = (int *)c->dkg[4].get(4 * (pe.size() + pk.size()));
+    uint8_t *M = (uint8_t *)c->dkg[5].get((size_t)m * k + 16);
+    if (!dpe || !M) { set_err("device allocation failed"); return -1; }
+    std::vector<int> both(pe);
+    both.insert(both.end(), pk.begin(), pk.end());
+    hipMemcpyAsync(dpe, both.data(), 4 * both.size(), hipMemcpyHostToDevice, s);
+    uint8_t *ok = M + (size_t)m * k;
+    lcbk_rs_matrix(s, dpe, m, dpe + m, k, n, M, ok);
+    lcbk_rs_apply(s, M, ok, m, k, d_known, S, dpe, d_out);
+    *d_ok = ok;
+    return launch_ok("rs launch") ? 0 : -1;
+}
+}  // namespace
+extern "C" int lcb_rs_encode(uint8_t *shards_out, const uint8_t *input, size_t input_len, int n_shards, int erasures) {
+    SYNC_CTX_OR(c, -1)
+    int k = n_shards - erasures;
+    if (n_shards <= 0 || erasures < 0 || k <= 0 || input_len % (size_t)k) {
+        set_err("rs encode: need 0 <= erasures < shards and input length divisible by the data shards");
+        return -1;
+    }
+    size_t S = input_len / (size_t)k;
+    if (erasures == 0 || S == 0) { memcpy(shards_out, input, input_len); return 0; }
+    Enq q(c, c->stream);
+    hipStream_t s = c->stream;
+    uint8_t *dout = (uint8_t *)c->out[0].get(S * n_shards);
+    if (!dout) { set_err("device allocation failed"); return -1; }
+    hipMemcpyAsync(dout, input, input_len, hipMemcpyHostToDevice, s);   // data shards stay in place (systematic)
+    std::vector<int> pe, pk;
+    for (int j = k; j < n_shards; j++) pe.push_back(j);
+    for (int j = 0; j < k; j++) pk.push_back(j);
+    uint8_t *dok;
+    if (rs_enqueue(c, dout, dout, pe, pk, n_shards, S, s, &dok)) return -1;
+    uint8_t ok = 0;
+    hipMemcpyAsync(shards_out, dout, S * n_shards, hipMemcpyDeviceToHost, s);
+    hipMemcpyAsync(&ok, dok, 1, hipMemcpyDeviceToHost, s);
+    if (!sync_check(c, "rs encode")) return -1;
+    if (!ok) { set_err("rs encode: parity positions are not independent (more than 255 shards)"); return -1; }
+    return 0;
+}
+extern "C" int lcb_rs_decode(uint8_t *out, const uint8_t *echo_data, const int32_t *from, int n_echos, size_t shard_size,
+                             int n_shards, int erasures) {
+    SYNC_CTX_OR(c, -1)
+    int k = n_shards - erasures;
+    if (n_shards <= 0 || erasures < 0 || k <= 0 || n_echos != k) {
+        set_err("rs decode: need exactly shards - erasures echoes (DecodeFromEchos asserts N - 2F)");
+        return -1;
+    }
+    std::vector<char> have(n_shards, 0);
+    std::vector<int> pe, pk;
+    for (int e = 0; e < n_echos; e++) {
+        if (from[e] < 0 || from[e] >= n_shards || have[from[e]]) { set_err("rs decode: bad or duplicate echo index"); return -1; }
+        have[from[e]] = 1;
+        pk.push_back(from[e]);
+    }
+    for (int j = 0; j < n_shards; j++) if (!have[j]) pe.push_back(j);
+    size_t S = shard_size;
+    if (S == 0) return 0;
+    Enq q(c, c->stream);
+    hipStream_t s = c->stream;
+    uint8_t *dout = (uint8_t *)c->out[0].get(S * n_shards);
+    const uint8_t *decho = up(c->in[0], echo_data, S * (size_t)n_echos, s);
+    if (!dout || !decho) { set_err("device allocation failed"); return -1; }
+    for (int e = 0; e < n_echos; e++)
+        hipMemcpyAsync(dout + (size_t)from[e] * S, decho + (size_t)e * S, S, hipMemcpyDeviceToDevice, s);
+    uint8_t ok = 1;
+    if (!pe.empty()) {
+        uint8_t *dok;
+        if (rs_enqueue(c, dout, decho, pe, pk, n_shards, S, s, &dok)) return -1;
+        hipMemcpyAsync(&ok, dok, 1, hipMemcpyDeviceToHost, s);
+    }
+    hipMemcpyAsync(out, dout, S * n_shards, hipMemcpyDeviceToHost, s);
+    if (!sync_check(c, "rs decode")) return -1;
+    if (!ok) { set_err("rs decode: erased positions share an evaluation point (more than 255 shards)"); return -1; }
+    return 0;
 }

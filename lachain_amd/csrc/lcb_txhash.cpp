@@ -27,7 +27,7 @@ const uint64_t MAX_INVOCATION = 0x7fffffffu;     // an item of 2^31 bytes or mor
 bool events_ready(lcb_ctx *c) {
     if (c->tx_ev_ready) return true;
     for (auto &e : c->tx_ev)
-        if (hipEventCreate(&e) != hipSuccess) { set_error("event creation"); return false; }
+        if (hipEventCreate(&e) != hipSuccess) { set_err("event creation"); return false; }
     c->tx_ev_ready = true;
     return true;
 }
@@ -42,7 +42,7 @@ bool common_ok(size_t n, const void *txs, const void *inv, const void *off, size
     else if (sigs_given && sig_len != (use_new_chain_id ? 66u : 65u)) why = "sig_len must be 65 (old chain id) or 66 (new)";
     if (!why) return true;
     snprintf(msg, sizeof msg, "%s: %s", what, why);
-    set_error(msg);
+    set_err(msg);
     return false;
 }
 // the host-pointer forms also read what the device forms must trust: offsets and To lengths
@@ -56,23 +56,18 @@ bool host_items_ok(const lcb_tx_fields *txs, const uint64_t *off, size_t n, cons
     }
     if (!why) return true;
     snprintf(msg, sizeof msg, "%s: %s", what, why);
-    set_error(msg);
+    set_err(msg);
     return false;
-}
-template <class T> T *upload(DevBuf &b, const T *src, size_t count, hipStream_t s) {
-    T *d = (T *)b.get(count * sizeof(T));
-    if (d && count) hipMemcpyAsync(d, src, count * sizeof(T), hipMemcpyHostToDevice, s);
-    return d;
 }
 
 // hashing alone, device pointers; the events of a later phase collapse onto the hashing's end
 int hash_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *raw32, uint8_t *full32, uint8_t *match, const uint8_t *txs,
                  const uint8_t *inv, const uint64_t *off, const uint8_t *sigs, size_t sig_len, const uint8_t *claimed,
                  size_t n, int32_t chain_id, bool last_phase) {
-    if (((uintptr_t)txs | (uintptr_t)off) & 7) { set_error("tx hash: txs and inv_off must be 8-byte aligned"); return -1; }
+    if (((uintptr_t)txs | (uintptr_t)off) & 7) { set_err("tx hash: txs and inv_off must be 8-byte aligned"); return -1; }
     if (!events_ready(c)) return -1;
     uint32_t *long_ws = (uint32_t *)c->tx[12].get(4 * (n + 1));    // k_tx_hash's list of long items
-    if (!long_ws) { set_error("device allocation failed"); return -1; }
+    if (!long_ws) { set_err("device allocation failed"); return -1; }
     (void)hipEventRecord(c->tx_ev[0], s);
     lcbk_tx_hash(s, txs, inv, off, sigs, (u32)sig_len, claimed, (u32)chain_id, (u32)n, raw32, full32, match, long_ws);
     (void)hipEventRecord(c->tx_ev[1], s);
@@ -92,7 +87,7 @@ int receipts_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *accept, uint8_t *detail
     if (n) {
         uint8_t *raw = (uint8_t *)c->tx[0].get(32 * n), *flags = (uint8_t *)c->tx[1].get(2 * n);
         uint8_t *addr = (uint8_t *)c->tx[2].get(20 * n);
-        if (!raw || !flags || !addr) { set_error("device allocation failed"); return -1; }
+        if (!raw || !flags || !addr) { set_err("device allocation failed"); return -1; }
         uint8_t *match = flags, *rec_ok = flags + n;
         if (hash_enqueue(c, s, raw, nullptr, match, txs, inv, off, sigs, sig_len, claimed, n, chain_id, false)) return -1;
         if (lcb_ctx_ecdsa_recover_hashed_dev(c, nullptr, addr, rec_ok, raw, sigs, sig_len, n, use_new_chain_id, chain_id, s))
@@ -107,7 +102,7 @@ int receipts_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *accept, uint8_t *detail
     (void)hipEventRecord(c->tx_ev[2], s);
     if (n_blocks) {
         uint8_t *roots = (uint8_t *)c->tx[3].get(33 * n_blocks);
-        if (!roots) { set_error("device allocation failed"); return -1; }
+        if (!roots) { set_err("device allocation failed"); return -1; }
         if (lcb_ctx_merkle_root_dev(c, roots, roots + 32 * n_blocks, claimed, tx_off, n_blocks, n, s)) return -1;
         lcbk_tx_root_ok(s, roots, expected_roots, (u32)n_blocks, root_ok);
     }
@@ -123,9 +118,9 @@ int receipts_dev(lcb_ctx *ctx, uint8_t *accept, uint8_t *detail, uint8_t *root_o
     lcb_ctx *c = ctx_resolve(ctx);
     if (!c) return -1;
     if (!common_ok(n, txs, inv, off, sig_len, true, use_new_chain_id, chain_id, what)) return -1;
-    if (n && (!accept || !sigs || !claimed)) { set_error("receipts verify: accept, sigs and hashes32 are required"); return -1; }
+    if (n && (!accept || !sigs || !claimed)) { set_err("receipts verify: accept, sigs and hashes32 are required"); return -1; }
     if (blocks && (n_blocks > MAX_ITEMS || (n_blocks && (!tx_off || !expected_roots || !root_ok)))) {
-        set_error("block txs verify: tx_off, expected_roots and root_ok are required (at most 2^31 - 1 blocks)");
+        set_err("block txs verify: tx_off, expected_roots and root_ok are required (at most 2^31 - 1 blocks)");
         return -1;
     }
     Enq q(c, (hipStream_t)stream);
@@ -141,18 +136,18 @@ int receipts_host(uint8_t *accept, uint8_t *detail, uint8_t *root_ok, const lcb_
     lcb_ctx *c = ctx_sync();
     if (!c) return -1;
     if (!common_ok(n, txs, inv, off, sig_len, true, use_new_chain_id, chain_id, what)) return -1;
-    if (n && (!accept || !sigs || !claimed)) { set_error("receipts verify: accept, sigs and hashes32 are required"); return -1; }
+    if (n && (!accept || !sigs || !claimed)) { set_err("receipts verify: accept, sigs and hashes32 are required"); return -1; }
     if (!host_items_ok(txs, off, n, what)) return -1;
     if (!blocks) n_blocks = 0;
     if (n_blocks) {
         if (n_blocks > MAX_ITEMS || !tx_off || !expected_roots || !root_ok) {
-            set_error("block txs verify: tx_off, expected_roots and root_ok are required (at most 2^31 - 1 blocks)");
+            set_err("block txs verify: tx_off, expected_roots and root_ok are required (at most 2^31 - 1 blocks)");
             return -1;
         }
         for (size_t b = 0; b < n_blocks; b++)
-            if (tx_off[b + 1] < tx_off[b]) { set_error("block txs verify: block offsets must not decrease"); return -1; }
+            if (tx_off[b + 1] < tx_off[b]) { set_err("block txs verify: block offsets must not decrease"); return -1; }
         if (tx_off[0] != 0 || tx_off[n_blocks] != n) {
-            set_error("block txs verify: tx_off must run from 0 to n");
+            set_err("block txs verify: tx_off must run from 0 to n");
             return -1;
         }
     }
@@ -162,16 +157,16 @@ int receipts_host(uint8_t *accept, uint8_t *detail, uint8_t *root_ok, const lcb_
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     Enq q(c, c->stream);
     hipStream_t s = c->stream;
-    const lcb_tx_fields *dtx = upload(c->tx[4], txs, n, s);
-    const uint8_t *dinv = upload(c->tx[5], n ? inv + off[0] : inv, (size_t)rel[n], s);
-    const uint64_t *doff = upload(c->tx[6], rel.data(), n + 1, s);
-    const uint8_t *dsig = upload(c->tx[7], sigs, sig_len * n, s);
-    const uint8_t *dclaim = upload(c->tx[8], claimed, 32 * n, s);
+    const lcb_tx_fields *dtx = up(c->tx[4], txs, n, s);
+    const uint8_t *dinv = up(c->tx[5], n ? inv + off[0] : inv, (size_t)rel[n], s);
+    const uint64_t *doff = up(c->tx[6], rel.data(), n + 1, s);
+    const uint8_t *dsig = up(c->tx[7], sigs, sig_len * n, s);
+    const uint8_t *dclaim = up(c->tx[8], claimed, 32 * n, s);
     uint8_t *dout = (uint8_t *)c->tx[9].get(2 * n + n_blocks);
-    const uint64_t *dtoff = n_blocks ? upload(c->tx[10], tx_off, n_blocks + 1, s) : nullptr;
-    const uint8_t *dexp = n_blocks ? upload(c->tx[11], expected_roots, 32 * n_blocks, s) : nullptr;
+    const uint64_t *dtoff = n_blocks ? up(c->tx[10], tx_off, n_blocks + 1, s) : nullptr;
+    const uint8_t *dexp = n_blocks ? up(c->tx[11], expected_roots, 32 * n_blocks, s) : nullptr;
     if (!dtx || !dinv || !doff || !dsig || !dclaim || !dout || (n_blocks && (!dtoff || !dexp))) {
-        set_error("device allocation failed");
+        set_err("device allocation failed");
         return -1;
     }
     uint8_t *dacc = dout, *ddet = dout + n, *drok = dout + 2 * n;
@@ -181,7 +176,7 @@ int receipts_host(uint8_t *accept, uint8_t *detail, uint8_t *root_ok, const lcb_
     if (n) hipMemcpyAsync(accept, dacc, n, hipMemcpyDeviceToHost, s);
     if (n && detail) hipMemcpyAsync(detail, ddet, n, hipMemcpyDeviceToHost, s);
     if (n_blocks) hipMemcpyAsync(root_ok, drok, n_blocks, hipMemcpyDeviceToHost, s);
-    return sync_ok(c, what) ? 0 : -1;
+    return sync_check(c, what) ? 0 : -1;
 }
 
 }  // namespace
@@ -225,18 +220,18 @@ extern "C" int lcb_tx_hash_batch(uint8_t *raw32_out, uint8_t *full32_out, const 
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     Enq q(c, c->stream);
     hipStream_t s = c->stream;
-    const lcb_tx_fields *dtx = upload(c->tx[4], txs, n, s);
-    const uint8_t *dinv = upload(c->tx[5], invocations + inv_off[0], (size_t)rel[n], s);
-    const uint64_t *doff = upload(c->tx[6], rel.data(), n + 1, s);
-    const uint8_t *dsig = sigs ? upload(c->tx[7], sigs, sig_len * n, s) : nullptr;
+    const lcb_tx_fields *dtx = up(c->tx[4], txs, n, s);
+    const uint8_t *dinv = up(c->tx[5], invocations + inv_off[0], (size_t)rel[n], s);
+    const uint64_t *doff = up(c->tx[6], rel.data(), n + 1, s);
+    const uint8_t *dsig = sigs ? up(c->tx[7], sigs, sig_len * n, s) : nullptr;
     uint8_t *dout = (uint8_t *)c->tx[9].get(64 * n);
-    if (!dtx || !dinv || !doff || (sigs && !dsig) || !dout) { set_error("device allocation failed"); return -1; }
+    if (!dtx || !dinv || !doff || (sigs && !dsig) || !dout) { set_err("device allocation failed"); return -1; }
     uint8_t *draw = raw32_out ? dout : nullptr, *dfull = sigs && full32_out ? dout + 32 * n : nullptr;
     if (hash_enqueue(c, s, draw, dfull, nullptr, (const uint8_t *)dtx, dinv, doff, dsig, sig_len, nullptr, n, chain_id, true))
         return -1;
     if (draw) hipMemcpyAsync(raw32_out, draw, 32 * n, hipMemcpyDeviceToHost, s);
     if (dfull) hipMemcpyAsync(full32_out, dfull, 32 * n, hipMemcpyDeviceToHost, s);
-    return sync_ok(c, "tx hash") ? 0 : -1;
+    return sync_check(c, "tx hash") ? 0 : -1;
 }
 
 // ------------------------------------------------------------------ VerifyTransactionImmediately
@@ -293,11 +288,11 @@ extern "C" int lcb_ctx_tx_phase_ms(lcb_ctx *ctx, float ms[3]) {
     lcb_ctx *c = ctx_resolve(ctx);
     if (!c) return -1;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (!c->tx_ran) { set_error("no transaction hashing has run in this context"); return -1; }
+    if (!c->tx_ran) { set_err("no transaction hashing has run in this context"); return -1; }
     for (int k = 0; k < 3; k++) {
         hipError_t e = hipEventSynchronize(c->tx_ev[k + 1]);
         if (e == hipSuccess) e = hipEventElapsedTime(&ms[k], c->tx_ev[k], c->tx_ev[k + 1]);
-        if (e != hipSuccess) { set_error("tx phase timing", e); return -1; }
+        if (e != hipSuccess) { set_err("tx phase timing", e); return -1; }
     }
     return 0;
 }

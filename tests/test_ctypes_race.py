@@ -8,7 +8,7 @@ Finding: ctypes reads the converters and restype under the GIL before it release
 does not use them after the call, and the types involved (c_int, c_size_t, POINTER(...) types, None) are never
 freed, so the re-configuration is harmless — the process survives and every product is exact.  The round-3 crash
 therefore did not come from the binding; the library-side cause (a half-built per-thread staging area written
-through a null pinned buffer, lcb_host.cpp stage_ready) is fixed and tested in tests/test_gpu_failures.py."""
+through a null pinned buffer, lcb_mcl.cpp stage_ready) is fixed and tested in tests/test_gpu_failures.py."""
 import os
 import subprocess
 import sys

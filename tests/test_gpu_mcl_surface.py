@@ -1,4 +1,4 @@
-"""The mcl single-element surface on its batch / cooperative kernels (lcb_host.cpp "mcl surface" section):
+"""The mcl single-element surface on its batch / cooperative kernels (lcb_mcl.cpp, the second half):
 mclBn_pairing (one-group nine-lane check), mclBn_finalExp, mclBnG1_mulVec, G1 / G2 Lagrange interpolation and
 G1 / G2 EvaluatePolynomial against the oracle, bit-exact on the wire encodings; and the per-thread staging
 (single operations from several threads at once).
@@ -192,7 +192,7 @@ def test_evaluate_polynomial_matches_horner(mcl, g):
 
 
 def test_g1_evaluate_polynomial_off_subgroup_and_long(mcl):
-    """G1 EvaluatePolynomial runs as independent terms [x^i mod #E(Fp)] c_i (lcb_host.cpp eval_poly_g1_terms): the
+    """G1 EvaluatePolynomial runs as independent terms [x^i mod #E(Fp)] c_i (lcb_mcl.cpp eval_poly_g1_terms): the
     Horner value for coefficients outside G1 too (the order-3 point and a random on-curve point, G1.FromBytes accepts
     them), for x = 0, 1, -1, -3 and random x, for a polynomial longer than one block of terms, and with the point at
     infinity among the coefficients."""
