@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""tools/asm_sim.py — single-lane interpreter for the gfx950 leaf routines in lachain_amd/csrc/asm_routines.hpp.
+"""tools/asm_sim.py — single-lane interpreter for the generated gfx950 routine libraries (asm_routines.hpp,
+asm_tower.hpp).
 
-Executes the generated routine text (the subset of VOP2/VOP3/SOP1 instructions tools/gen_asm.py emits) for
-one lane with Python integers, so the generator's arithmetic and its register contract (which VGPRs/SGPRs a
-routine may write) can be checked on the CPU, without a GPU.  Used by tests/test_asm_routines.py.
+Executes a library's text (the subset of VOP3 / SOP / global / LDS instructions the generators emit) for one lane
+with Python integers: registers, SCC, labels, branches, calls with a return stack, global memory (a dict of 32-bit
+words keyed by byte address) and LDS.  The generators' arithmetic and their register contract (which registers a
+routine may write) are checked with it on the CPU by tests/test_asm_routines.py and tests/test_asm_tower.py.
 """
 import os
 import re
@@ -11,31 +13,32 @@ import re
 M32 = (1 << 32) - 1
 HERE = os.path.dirname(os.path.abspath(__file__))
 HPP = os.path.join(HERE, "..", "lachain_amd", "csrc", "asm_routines.hpp")
-
-
 TOWER_HPP = os.path.join(HERE, "..", "lachain_amd", "csrc", "asm_tower.hpp")
 
 
-def load_library(path=HPP, macro="LCB_ASM_LIBRARY_TEXT"):
-    """-> {label: [(mnemonic, [operands])]} parsed from the library text macro."""
+def load_program(path=TOWER_HPP, macro="LCB_ASM_TOWER_LIBRARY_TEXT"):
+    """-> (instructions [(mnemonic, [operands])], {label: index}) parsed from the library text macro.  The
+    `.p2align` in front of every routine stays in the stream as an instruction that raises: a routine that runs off
+    its end stops there instead of sliding into the next one."""
     src = open(path).read()
     body = src[src.index("#define " + macro):]
     body = body[:body.index('    ""\n')]
-    routines, cur = {}, None
+    prog, labels = [], {}
     for raw in re.findall(r'"(.*?)\\n"', body):
         line = raw.strip()
-        if not line or line.startswith("."):
+        if not line or (line.startswith(".") and not line.startswith(".p2align")):
             continue
         if line.endswith(":"):
-            cur = line[:-1]
-            routines[cur] = []
-            continue
-        if cur is None:
+            labels[line[:-1]] = len(prog)
             continue
         mn, _, rest = line.partition(" ")
         ops = [o.strip() for o in rest.split(",")] if rest else []
-        routines[cur].append((mn, ops))
-    return routines
+        prog.append((mn, ops))
+    return prog, labels
+
+
+def load_library(path=HPP, macro="LCB_ASM_LIBRARY_TEXT"):
+    return load_program(path, macro)
 
 
 def _regs(op):
@@ -50,11 +53,12 @@ def _regs(op):
     return None, None
 
 
-class Lane:
+class ProgLane:
     def __init__(self):
         self.v, self.s, self.a = {}, {}, {}
         self.written_v, self.written_s, self.written_a = set(), set(), set()
         self.counts = {}
+        self.mem, self.lds, self.scc = {}, {}, 0
 
     def get(self, op):
         kind, rr = _regs(op)
@@ -80,97 +84,6 @@ class Lane:
             f[r] = (val >> (32 * k)) & M32
             w.add(r)
 
-
-def run(routine, lane, routines=None):
-    target = None
-    for mn, ops in routine:
-        g = lane.get
-        lane.counts[mn] = lane.counts.get(mn, 0) + 1
-        if mn == "v_mad_u64_u32":
-            r = g(ops[2]) * g(ops[3]) + g(ops[4])
-            lane.put(ops[0], r & ((1 << 64) - 1)); lane.put(ops[1], r >> 64)
-        elif mn in ("v_add_co_u32_e64", "v_addc_co_u32_e64"):
-            r = g(ops[2]) + g(ops[3]) + (lane.getmask(ops[4]) if mn == "v_addc_co_u32_e64" else 0)
-            lane.put(ops[0], r & M32); lane.put(ops[1], r >> 32)
-        elif mn in ("v_sub_co_u32_e64", "v_subb_co_u32_e64"):
-            r = g(ops[2]) - g(ops[3]) - (lane.getmask(ops[4]) if mn == "v_subb_co_u32_e64" else 0)
-            lane.put(ops[0], r & M32); lane.put(ops[1], 1 if r < 0 else 0)
-        elif mn == "v_cndmask_b32_e64":
-            lane.put(ops[0], g(ops[2]) if lane.getmask(ops[3]) else g(ops[1]))
-        elif mn == "v_alignbit_b32":         # ({S0, S1} >> S2[4:0]) low word
-            r = ((g(ops[1]) << 32) | g(ops[2])) >> (g(ops[3]) & 31)
-            lane.put(ops[0], r & M32)
-        elif mn == "v_lshlrev_b32":
-            lane.put(ops[0], (g(ops[2]) << (g(ops[1]) & 31)) & M32)
-        elif mn == "v_mul_lo_u32":
-            lane.put(ops[0], (g(ops[1]) * g(ops[2])) & M32)
-        elif mn in ("v_mov_b32", "s_mov_b32", "v_accvgpr_read_b32", "v_accvgpr_write_b32"):
-            lane.put(ops[0], g(ops[1]))
-        elif mn in ("s_nop", "s_getpc_b64", "s_addc_u32"):
-            pass
-        elif mn == "s_add_u32":             # call sequence: remember the target label
-            target = ops[2].split("@")[0]
-        elif mn == "s_swappc_b64":
-            run(routines[target], lane, routines)
-        elif mn == "s_setpc_b64":
-            return
-        elif mn == "s_endpgm":
-            return
-        else:
-            raise NotImplementedError(mn)
-    raise RuntimeError("routine fell off its end without s_setpc_b64")
-
-
-def call(routines, label, inputs, agprs=None):
-    """inputs: {first VGPR: 12-limb integer}; agprs: {first AGPR: 12-limb integer}.
-    Returns (lane, reader(first VGPR) -> integer)."""
-    lane = Lane()
-    for base, val in inputs.items():
-        for j in range(12):
-            lane.v[base + j] = (val >> (32 * j)) & M32
-    for base, val in (agprs or {}).items():
-        for j in range(12):
-            lane.a[base + j] = (val >> (32 * j)) & M32
-    run(routines[label], lane, routines)
-
-    def read(base):
-        return sum(lane.v[base + j] << (32 * j) for j in range(12))
-    return lane, read
-
-
-# ---------------------------------------------------------------- whole-library programs (asm_tower.hpp, round 5)
-# Labels, branches, calls with a return stack, SALU, global memory (a dict of 32-bit words keyed by byte address) and
-# LDS: enough to run lcb_r_pow_z / lcb_r_fp12_mul_n and their callees for one lane.
-def load_program(path=TOWER_HPP, macro="LCB_ASM_TOWER_LIBRARY_TEXT"):
-    """-> (instructions [(mnemonic, [operands])], {label: index})"""
-    src = open(path).read()
-    body = src[src.index("#define " + macro):]
-    body = body[:body.index('    ""\n')]
-    prog, labels = [], {}
-    for raw in re.findall(r'"(.*?)\\n"', body):
-        line = raw.strip()
-        if not line or line.startswith("."):
-            continue
-        if line.endswith(":"):
-            labels[line[:-1]] = len(prog)
-            continue
-        mn, _, rest = line.partition(" ")
-        ops = [o.strip() for o in rest.split(",")] if rest else []
-        prog.append((mn, ops))
-    return prog, labels
-
-
-def _split_off(op):
-    """'v[72:75] offset:1024' -> ('v[72:75]', 1024)"""
-    m = re.fullmatch(r"(\S+)\s+offset:(\d+)", op)
-    return (m.group(1), int(m.group(2))) if m else (op, 0)
-
-
-class ProgLane(Lane):
-    def __init__(self):
-        super().__init__()
-        self.mem, self.lds, self.scc = {}, {}, 0
-
     def load(self, addr, n):
         out = 0
         for k in range(n):
@@ -185,7 +98,14 @@ class ProgLane(Lane):
             self.mem[addr + 4 * k] = (val >> (32 * k)) & M32
 
 
+def _split_off(op):
+    """'v[72:75] offset:1024' -> ('v[72:75]', 1024)"""
+    m = re.fullmatch(r"(\S+)\s+offset:(\d+)", op)
+    return (m.group(1), int(m.group(2))) if m else (op, 0)
+
+
 def run_program(prog, labels, entry, lane, max_steps=50_000_000):
+    """run from label `entry` until the `s_setpc_b64` that returns from it"""
     pc, stack, target = labels[entry], [], None
     g = lane.get
     for _ in range(max_steps):
@@ -270,6 +190,23 @@ def run_program(prog, labels, entry, lane, max_steps=50_000_000):
                 addr, off = _split_off(ops[1])
                 a = g(addr) + off
                 lane.put(ops[0], sum(lane.lds[a + 4 * k] << (32 * k) for k in range(4)))
+        elif mn == ".p2align":
+            raise RuntimeError(f"{entry}: a routine fell off its end without s_setpc_b64")
         else:
             raise NotImplementedError(mn)
     raise RuntimeError("step limit")
+
+
+def call(lib, label, inputs, agprs=None):
+    """run routine `label` of lib = (prog, labels) on a fresh lane.  inputs: {first VGPR: 12-limb integer}; agprs:
+    {first AGPR: 12-limb integer}.  Returns (lane, reader(first VGPR) -> integer)."""
+    lane = ProgLane()
+    for f, vals in ((lane.v, inputs), (lane.a, agprs or {})):
+        for base, val in vals.items():
+            for j in range(12):
+                f[base + j] = (val >> (32 * j)) & M32
+    run_program(*lib, label, lane)
+
+    def read(base):
+        return sum(lane.v[base + j] << (32 * j) for j in range(12))
+    return lane, read

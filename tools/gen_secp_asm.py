@@ -4,42 +4,31 @@ field product and square (p = 2^256 - 2^32 - 977) used by k_secp.hip.
 
 Each function is one asm block whose operands are pinned to v0..v15 (inputs / output); its temporaries are listed
 as clobbers, so the compiler moves values in and out but never splits the carry chains.  Product: column (product)
-scanning with a 64-bit accumulator pair and a carry-count word rotating through a 4-register ring (one
-v_mad_u64_u32 + one v_addc per partial product, no zeroing: the first carry add of a column writes 0 + 0 + carry),
-as in tools/gen_asm.py for BLS12-381.  Square: the 28 cross products once, doubled by a 1-bit shift, plus the 8
-squares.  Reduction: t = lo + hi * 977 + (hi << 32) column by column, then the top word (< 2^34) folded once more by
-C = 2^32 + 977, and a final conditional + C if that wraps (the result is < 2^256, congruent mod p: "weakly reduced",
-the representation secp.hpp uses).  Carries ride in VCC and are only read through VOP2 (e32) forms: on gfx940+ an
-explicit SGPR read right after a VALU writes that SGPR needs two wait states that inline assembly does not get, the
-implicit VCC read of VOP2 does not (tools/gen_asm.py uses the same rule).  977 and 0 live in VGPRs (gfx9 VOP3 takes
-no literal operands, VOP2 needs a VGPR second source).
+scanning over the accumulator ring of tools/asm_core.py, at 8 limbs; it keeps its own emitter because its carries
+ride in VCC through VOP2 (e32) forms, its zero is a VGPR and its top word leaves through the ring.  Square: the 28
+cross products once, doubled by a 1-bit shift, plus the 8 squares.  Reduction: t = lo + hi * 977 + (hi << 32) column
+by column, then the top word (< 2^34) folded once more by C = 2^32 + 977, and a final conditional + C if that wraps
+(the result is < 2^256, congruent mod p: "weakly reduced", the representation secp.hpp uses).  977 and 0 live in
+VGPRs (gfx9 VOP3 takes no literal operands, VOP2 needs a VGPR second source).
 
 Verified by tests/test_secp_emul.py on the CPU only through the C++ path; the asm is checked on the GPU by
 tests/test_gpu_ecdsa.py (every decision against the oracle) and by tools/emul/secp_stage_dump.hip diffs.
 """
 import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from asm_core import c_quote, clobbers, ring  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lachain_amd", "csrc", "secp_asm.hpp")
-
-
-class Asm:
-    def __init__(self):
-        self.lines = []
-
-    def __call__(self, s):
-        self.lines.append(s)
-
-
 ZERO = 41
 
 
-def product(a, A, B, T, ring):
-    """T[0..15] <- A[0..7] * B[0..7] (A, B, T register numbers); ring: 4 registers, ring[0] even"""
-    def rk(k):
-        r = ring
-        return (r[0], r[1], r[3]) if k % 2 == 0 else (r[2], r[3], r[1])
-    a(f"v_mov_b32 v{ring[0]}, 0")
-    a(f"v_mov_b32 v{ring[1]}, 0")
+def product(a, A, B, T, acc):
+    """T[0..15] <- A[0..7] * B[0..7] (A, B, T register numbers), appended through a; acc: the ring block (even)"""
+    rk = lambda k: ring(acc, k)                                                    # noqa: E731
+    a(f"v_mov_b32 v{acc}, 0")
+    a(f"v_mov_b32 v{acc + 1}, 0")
     for k in range(15):
         L, H, C = rk(k)
         terms = [(i, k - i) for i in range(8) if 0 <= k - i <= 7]
@@ -54,14 +43,12 @@ def product(a, A, B, T, ring):
     a(f"v_mov_b32 v{T[15]}, v{L}")
 
 
-def square(a, A, T, ring):
+def square(a, A, T, acc):
     """T <- A^2: cross products once (columns 1..13), doubled, plus the squares"""
-    def rk(k):
-        r = ring
-        return (r[0], r[1], r[3]) if k % 2 == 0 else (r[2], r[3], r[1])
+    rk = lambda k: ring(acc, k)                                                    # noqa: E731
     a(f"v_mov_b32 v{T[0]}, 0")
-    a(f"v_mov_b32 v{ring[2]}, 0")
-    a(f"v_mov_b32 v{ring[3]}, 0")
+    a(f"v_mov_b32 v{acc + 2}, 0")
+    a(f"v_mov_b32 v{acc + 3}, 0")
     for k in range(1, 14):
         L, H, C = rk(k)
         terms = [(i, k - i) for i in range(8) if i < k - i <= 7]
@@ -79,9 +66,8 @@ def square(a, A, T, ring):
         a(f"v_alignbit_b32 v{T[k]}, v{T[k]}, v{T[k - 1]}, 31")
     a(f"v_lshlrev_b32 v{T[0]}, 1, v{T[0]}")
     # + squares: a_i^2 at columns 2i, 2i+1, carry chained through the whole 512 bits
-    sq = ring  # two pairs
-    for i in range(8):
-        p0, p1 = (sq[0], sq[1]) if i % 2 == 0 else (sq[2], sq[3])
+    for i in range(8):                                     # the ring block as two pairs
+        p0, p1 = (acc, acc + 1) if i % 2 == 0 else (acc + 2, acc + 3)
         a(f"v_mul_lo_u32 v{p0}, v{A[i]}, v{A[i]}")
         a(f"v_mul_hi_u32 v{p1}, v{A[i]}, v{A[i]}")
         if i == 0:
@@ -154,8 +140,12 @@ def addsub_lines(sub):
     return L
 
 
+def block(lines):
+    return "        " + c_quote(lines, end_last=True)
+
+
 def addsub_fn(name, sub, comment):
-    body = "\n".join(f'        "{l}\\n\\t"' for l in addsub_lines(sub))
+    body = block(addsub_lines(sub))
     outs = ", ".join(f'"=&v"(r.v[{i}])' for i in range(8)) + ', "=&v"(t), "=&v"(u), "=&v"(z)'
     ins = ", ".join(f'"v"(a.v[{i}])' for i in range(8)) + ", " + ", ".join(f'"v"(b.v[{i}])' for i in range(8))
     return "\n".join([
@@ -171,29 +161,22 @@ def addsub_fn(name, sub, comment):
     ])
 
 
-def block(lines):
-    return "\n".join(f'        "{l}\\n\\t"' for l in lines)
-
-
-def gen():
+def emit():
+    """-> (header text, instructions of the product, of the square)"""
     A = list(range(0, 8))
     B = list(range(8, 16))
     T = list(range(16, 32))
-    ring = [32, 33, 34, 35]
+    ACC = 32
     X = [36, 37, 38, 39]
     K = 40
-    m = Asm()
-    m(f"v_mov_b32 v{K}, 977")
-    m(f"v_mov_b32 v{ZERO}, 0")
-    product(m, A, B, T, ring)
-    reduce(m, T, A, X, K)
-    s = Asm()
-    s(f"v_mov_b32 v{K}, 977")
-    s(f"v_mov_b32 v{ZERO}, 0")
-    square(s, A, T, ring)
-    reduce(s, T, A, X, K)
-    clob = ", ".join(f'"v{i}"' for i in range(16, 42)) + ', "vcc"'
-    clob_sq = ", ".join(f'"v{i}"' for i in range(8, 42)) + ', "vcc"'
+    m = [f"v_mov_b32 v{K}, 977", f"v_mov_b32 v{ZERO}, 0"]
+    product(m.append, A, B, T, ACC)
+    reduce(m.append, T, A, X, K)
+    s = [f"v_mov_b32 v{K}, 977", f"v_mov_b32 v{ZERO}, 0"]
+    square(s.append, A, T, ACC)
+    reduce(s.append, T, A, X, K)
+    clob = clobbers(v=range(16, 42), flags=["vcc"])
+    clob_sq = clobbers(v=range(8, 42), flags=["vcc"])
     out = [
         "// GENERATED by tools/gen_secp_asm.py — do not edit.",
         "// secp256k1 field product / square (p = 2^256 - 2^32 - 977) as gfx950 inline assembly; see the generator.",
@@ -205,7 +188,7 @@ def gen():
         "// a * b, weakly reduced (< 2^256, congruent mod p)",
         "__device__ __forceinline__ u32x8 secp_asm_mul(u32x8 a, u32x8 b) {",
         "    asm volatile(",
-        block(m.lines),
+        block(m),
         '        : "+{v[0:7]}"(a), "+{v[8:15]}"(b)',
         "        :",
         f"        : {clob});",
@@ -216,7 +199,7 @@ def gen():
         "// a^2, weakly reduced",
         "__device__ __forceinline__ u32x8 secp_asm_sqr(u32x8 a) {",
         "    asm volatile(",
-        block(s.lines),
+        block(s),
         '        : "+{v[0:7]}"(a)',
         "        :",
         f"        : {clob_sq});",
@@ -224,10 +207,19 @@ def gen():
         "}",
         "",
     ]
+    return "\n".join(out), len(m), len(s)
+
+
+def render():
+    return emit()[0]
+
+
+def main():
+    text, n_mul, n_sqr = emit()
     with open(OUT, "w") as f:
-        f.write("\n".join(out))
-    print("wrote", OUT, len(m.lines), "/", len(s.lines), "instructions")
+        f.write(text)
+    print("wrote", OUT, n_mul, "/", n_sqr, "instructions")
 
 
 if __name__ == "__main__":
-    gen()
+    main()

@@ -15,9 +15,9 @@ so nothing spills, and the arithmetic is lazy:
   so REDC returns < 2p): 6 x 144 + 4 x 156 MADs instead of 9 full products (1,800 MADs) per fp4.
   Granger-Scott combination z' = 3t -+ 2z in [0, 8p), reduced by three conditional subtractions (4p, 2p, p).
 
-Hazards: every VALU read of an SGPR (carry-in, lane mask) is at least 2 wait states after the VALU write of that
-SGPR, and an AGPR read at least 2 after its write (the pass `hazard_fix` inserts s_nop where interleaving of
-independent chains does not already provide the distance).  Routine outputs are fully reduced (< p).
+The emitters (chains, column products, reductions, interleaving) and their conventions are tools/asm_core.py's; every
+routine here goes through its `hazard_fix` pass, which inserts s_nop where the interleaving of independent chains does
+not already keep carry and AGPR reads two wait states behind their writes.  Routine outputs are fully reduced (< p).
 
 Routines:
   lcb_r_fp4sq    (internal) v[0:23] = a, v[24:47] = b (< p), p in v[188:199] -> A, B at FP4_OUT (< 2p)
@@ -26,11 +26,11 @@ Routines:
                  kernels call: the compiler never holds the AGPR accumulator, so it cannot copy it around)
 """
 import os
-import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from gen_asm import P, PL, N, PINV  # noqa: E402
+from asm_core import (N, P, PINV, PL, add_chain, c_quote, call_lines, clobbers, comba, condsub,  # noqa: E402
+                      hazard_fix, library_header, limbs, merge, mov_regs, movs_const, redc, sp, sub_chain)
 
 S_PINV = 88
 MAD_CARRY = [90, 92, 94, 86]                 # SGPR pairs of interleaved product / REDC chains
@@ -45,12 +45,7 @@ FP4_POOL = list(range(172))                  # lcb_r_fp4sq's value registers (v0
 FP4_ACCS = [172, 176, 180, 184]              # its 64-bit MAD accumulator rings (4 aligned blocks)
 A_PARK = 144                                 # a[144:167]: one double-width value parked across a product batch
 
-K5P2 = 5 * P * P
-K5P2L = [(K5P2 >> (32 * i)) & 0xFFFFFFFF for i in range(2 * N)]
-
-
-def limbs(x, n=N):
-    return [(x >> (32 * i)) & 0xFFFFFFFF for i in range(n)]
+K5P2L = limbs(5 * P * P, 2 * N)
 
 
 # ------------------------------------------------------------------ register allocation
@@ -86,177 +81,9 @@ class Pool:
         self.free |= set(regs)
 
 
-# ------------------------------------------------------------------ instruction streams
-def merge(streams):
-    """round-robin interleave of independent instruction lists"""
-    out, idx = [], [0] * len(streams)
-    while any(idx[k] < len(streams[k]) for k in range(len(streams))):
-        for k in range(len(streams)):
-            if idx[k] < len(streams[k]):
-                out.append(streams[k][idx[k]])
-                idx[k] += 1
-    return out
-
-
-def sp(c):
-    return f"s[{c}:{c + 1}]"
-
-
-def add_chain(r, x, y, c, first_carry_in=False):
-    """r = x + y over len(r) words; carry out in s[c]"""
-    s = [f"v_addc_co_u32_e64 v{r[0]}, {sp(c)}, v{x[0]}, v{y[0]}, {sp(c)}" if first_carry_in else
-         f"v_add_co_u32_e64 v{r[0]}, {sp(c)}, v{x[0]}, v{y[0]}"]
-    s += [f"v_addc_co_u32_e64 v{r[j]}, {sp(c)}, v{x[j]}, v{y[j]}, {sp(c)}" for j in range(1, len(r))]
-    return s
-
-
-def sub_chain(r, x, y, c):
-    """r = x - y over len(r) words; borrow out in s[c]"""
-    s = [f"v_sub_co_u32_e64 v{r[0]}, {sp(c)}, v{x[0]}, v{y[0]}"]
-    s += [f"v_subb_co_u32_e64 v{r[j]}, {sp(c)}, v{x[j]}, v{y[j]}, {sp(c)}" for j in range(1, len(r))]
-    return s
-
-
-def condsub(r, kp, tmp, c):
-    """r <- r - kp if r >= kp (12 words): tmp = r - kp; borrow ? r : tmp"""
-    s = sub_chain(tmp, r, kp, c)
-    s += [f"v_cndmask_b32_e64 v{r[j]}, v{tmp[j]}, v{r[j]}, {sp(c)}" for j in range(N)]
-    return s
-
-
-def movs_const(r, vals):
-    return [f"v_mov_b32 v{r[j]}, 0x{vals[j]:08x}" for j in range(len(r))]
-
-
-def ring(acc, k):
-    return (acc, acc + 1, acc + 3) if k % 2 == 0 else (acc + 2, acc + 3, acc + 1)
-
-
-def comba(chains):
-    """interleaved plain products T = a*b (24 words): chains = [dict(a, b, acc, out, c)].  out[k] is written at
-    the end of column k and may alias a[k-11] (k >= 11)."""
-    s = []
-    for ch in chains:
-        s += [f"v_mov_b32 v{ch['acc']}, 0", f"v_mov_b32 v{ch['acc'] + 1}, 0"]
-    for k in range(2 * N - 1):
-        terms = [(i, k - i) for i in range(max(0, k - (N - 1)), min(k, N - 1) + 1)]
-        for n_t, (i, j) in enumerate(terms):
-            for ch in chains:
-                L, H, C = ring(ch["acc"], k)
-                s.append(f"v_mad_u64_u32 v[{L}:{H}], {sp(ch['c'])}, v{ch['a'][i]}, v{ch['b'][j]}, v[{L}:{H}]")
-            for ch in chains:
-                L, H, C = ring(ch["acc"], k)
-                s.append(f"v_addc_co_u32_e64 v{C}, {sp(ch['c'])}, 0, {0 if n_t == 0 else 'v%d' % C}, {sp(ch['c'])}")
-        for ch in chains:
-            L, H, C = ring(ch["acc"], k)
-            s.append(f"v_mov_b32 v{ch['out'][k]}, v{L}")
-            if k == 2 * N - 2:
-                s.append(f"v_mov_b32 v{ch['out'][2 * N - 1]}, v{H}")
-            else:
-                L2, H2, C2 = ring(ch["acc"], k + 1)
-                s.append(f"v_mov_b32 v{L2}, v{H}")
-    return s
-
-
-def redc(chains, preg):
-    """interleaved Montgomery reductions (U + m p) / 2^384 of 24-word U: chains = [dict(u, m, acc, c)];
-    the result (< 2p for U < 9.84 p^2) lands in u[12:24]"""
-    s = []
-    for ch in chains:
-        s += [f"v_mov_b32 v{ch['acc']}, 0", f"v_mov_b32 v{ch['acc'] + 1}, 0"]
-    for k in range(2 * N):
-        for ch in chains:
-            L, H, C = ring(ch["acc"], k)
-            s.append(f"v_add_co_u32_e64 v{L}, {sp(ch['c'])}, v{L}, v{ch['u'][k]}")
-        for ch in chains:
-            L, H, C = ring(ch["acc"], k)
-            s.append(f"v_addc_co_u32_e64 v{H}, {sp(ch['c'])}, v{H}, 0, {sp(ch['c'])}")
-        for ch in chains:
-            L, H, C = ring(ch["acc"], k)
-            s.append(f"v_addc_co_u32_e64 v{C}, {sp(ch['c'])}, 0, 0, {sp(ch['c'])}")
-        terms = [(i, k - i) for i in range(max(0, k - (N - 1)), min(k - 1, N - 1) + 1)]
-        if k < N:
-            terms.append(("m", k))
-        for t in terms:
-            if t[0] == "m":
-                for ch in chains:
-                    L, H, C = ring(ch["acc"], k)
-                    s.append(f"v_mul_lo_u32 v{ch['m'][k]}, v{L}, s{S_PINV}")
-                xs, y = [ch["m"][k] for ch in chains], preg[0]
-            else:
-                i, j = t
-                xs, y = [ch["m"][i] for ch in chains], preg[j]
-            for ch, x in zip(chains, xs):
-                L, H, C = ring(ch["acc"], k)
-                s.append(f"v_mad_u64_u32 v[{L}:{H}], {sp(ch['c'])}, v{x}, v{y}, v[{L}:{H}]")
-            for ch in chains:
-                L, H, C = ring(ch["acc"], k)
-                s.append(f"v_addc_co_u32_e64 v{C}, {sp(ch['c'])}, 0, v{C}, {sp(ch['c'])}")
-        for ch in chains:
-            L, H, C = ring(ch["acc"], k)
-            if k >= N:
-                s.append(f"v_mov_b32 v{ch['u'][k]}, v{L}")     # u[k] was consumed at the start of column k
-            if k < 2 * N - 1:
-                L2, H2, C2 = ring(ch["acc"], k + 1)
-                s.append(f"v_mov_b32 v{L2}, v{H}")
-    return s
-
-
-# ------------------------------------------------------------------ hazard pass
-_SREAD_E64 = ("v_addc_co_u32_e64", "v_subb_co_u32_e64", "v_cndmask_b32_e64")
-
-
-def _sgpr_pairs(txt):
-    return [(int(a), int(b)) for a, b in re.findall(r"s\[(\d+):(\d+)\]", txt)]
-
-
-def hazard_fix(lines):
-    """insert s_nop so that (1) a VALU read of an SGPR pair comes >= 2 wait states after a VALU wrote it and
-    (2) an AGPR read comes >= 2 wait states after its write.  Wait states = instructions issued in between
-    (+ s_nop n counts n + 1)."""
-    out = []
-    last_sw = {}     # sgpr pair -> position (in wait-state units) of the last VALU write
-    last_aw = {}     # agpr -> position of last write
-    pos = 0
-    for ln in lines:
-        mn = ln.split()[0] if ln.strip() else ""
-        need = 0
-        if mn.startswith("v_"):
-            ops = ln[len(mn):].split(",")
-            reads = []
-            if mn in _SREAD_E64:
-                reads = _sgpr_pairs(ops[-1])
-            for pr in reads:
-                if pr in last_sw:
-                    need = max(need, 2 - (pos - last_sw[pr] - 1))
-            if mn == "v_accvgpr_read_b32":
-                a = int(re.search(r"a(\d+)", ops[1]).group(1))
-                if a in last_aw:
-                    need = max(need, 2 - (pos - last_aw[a] - 1))
-        if need > 0:
-            out.append(f"s_nop {need - 1}")
-            pos += need
-        out.append(ln)
-        if mn.startswith("v_"):
-            ops = ln[len(mn):].split(",")
-            if mn in ("v_mad_u64_u32", "v_add_co_u32_e64", "v_addc_co_u32_e64", "v_sub_co_u32_e64",
-                      "v_subb_co_u32_e64"):
-                for pr in _sgpr_pairs(ops[1]):
-                    last_sw[pr] = pos
-            if mn == "v_accvgpr_write_b32":
-                last_aw[int(re.search(r"a(\d+)", ops[0]).group(1))] = pos
-        if mn.startswith("s_nop"):
-            pos += int(ln.split()[1]) + 1
-        else:
-            pos += 1
-    return out
-
-
-def call(label):
-    return [f"s_getpc_b64 s[{S_CALL}:{S_CALL + 1}]",
-            f"s_add_u32 s{S_CALL}, s{S_CALL}, {label}@rel32@lo+4",
-            f"s_addc_u32 s{S_CALL + 1}, s{S_CALL + 1}, {label}@rel32@hi+12",
-            f"s_swappc_b64 s[28:29], s[{S_CALL}:{S_CALL + 1}]"]
+def call(label, ret=28):
+    """call through s[26:27]; leaf routines return through s[28:29], the Fp12-level ones through s[30:31]"""
+    return call_lines(label, S_CALL, ret)
 
 
 # ------------------------------------------------------------------ lcb_r_fp4sq
@@ -333,7 +160,7 @@ def gen_fp4():
     chains = []
     for t, u in enumerate([A0u, A1u, B0u, B1u]):
         chains.append(dict(u=u, m=pool.take(N), acc=pool.take_acc(), c=MAD_CARRY[t]))
-    body += redc(chains, Pr)
+    body += redc(chains, Pr, S_PINV)
     outs = [u[N:] for u in (A0u, A1u, B0u, B1u)]
     txt = ["lcb_r_fp4sq:"] + hazard_fix(body + ["s_setpc_b64 s[28:29]"])
     used = pool.used_max
@@ -432,11 +259,8 @@ def gen_cyc_sqr_n():
             b += ["s_add_u32 s16, s16, s19", "s_addc_u32 s17, s17, 0"]
     b.append("s_waitcnt vmcnt(0)")
     b.append("lcb_cyc_sqr_n_loop:")
-    b += ["s_getpc_b64 s[26:27]",
-          "s_add_u32 s26, s26, lcb_r_cyc_sqr@rel32@lo+4",
-          "s_addc_u32 s27, s27, lcb_r_cyc_sqr@rel32@hi+12",
-          "s_swappc_b64 s[30:31], s[26:27]",
-          "s_sub_u32 s18, s18, 1",
+    b += call("lcb_r_cyc_sqr", 30)
+    b += ["s_sub_u32 s18, s18, 1",
           "s_cmp_lg_u32 s18, 0",
           "s_cbranch_scc1 lcb_cyc_sqr_n_loop",
           "s_nop 4",                       # AGPR writes by the squaring -> stores of them
@@ -500,17 +324,11 @@ def gen_redc2():
     accumulators v144..v151; returns through s[28:29].  One copy shared by every reduction of the Fp6 / line products
     keeps their code within the instruction cache."""
     b = redc([dict(u=F2_RE, m=list(range(0, 12)), acc=F2_ACCS[0], c=MAD_CARRY[0]),
-              dict(u=F2_IM, m=list(range(12, 24)), acc=F2_ACCS[1], c=MAD_CARRY[1])], PR)
+              dict(u=F2_IM, m=list(range(12, 24)), acc=F2_ACCS[1], c=MAD_CARRY[1])], PR, S_PINV)
     for _ in range(2):
         b += merge([condsub(F2_RE[N:], PR, list(range(24, 36)), LIN_CARRY[0]),
                     condsub(F2_IM[N:], PR, list(range(36, 48)), LIN_CARRY[1])])
     return ["lcb_r_redc2:"] + hazard_fix(b + ["s_setpc_b64 s[28:29]"])
-
-
-def call_redc2():
-    return [f"s_getpc_b64 s[{S_CALL}:{S_CALL + 1}]", f"s_add_u32 s{S_CALL}, s{S_CALL}, lcb_r_redc2@rel32@lo+4",
-            f"s_addc_u32 s{S_CALL + 1}, s{S_CALL + 1}, lcb_r_redc2@rel32@hi+12",
-            f"s_swappc_b64 s[28:29], s[{S_CALL}:{S_CALL + 1}]"]
 
 
 def quad_addr(base, q):
@@ -610,19 +428,7 @@ def fp6_operands(ks):
     if len(ks) == 2:
         s += merge([modadd(F2_YA, F2_YA, T2[:12], P0[:12], LIN_CARRY[0]),
                     modadd(F2_YB, F2_YB, T2[12:], P0[12:], LIN_CARRY[1])])
-    return s + call_fp2dw()
-
-
-def call_fp2dw():
-    return [f"s_getpc_b64 s[{S_CALL}:{S_CALL + 1}]", f"s_add_u32 s{S_CALL}, s{S_CALL}, lcb_r_fp2dw@rel32@lo+4",
-            f"s_addc_u32 s{S_CALL + 1}, s{S_CALL + 1}, lcb_r_fp2dw@rel32@hi+12",
-            f"s_swappc_b64 s[28:29], s[{S_CALL}:{S_CALL + 1}]"]
-
-
-def call_ret(label_, ret):
-    return [f"s_getpc_b64 s[{S_CALL}:{S_CALL + 1}]", f"s_add_u32 s{S_CALL}, s{S_CALL}, {label_}@rel32@lo+4",
-            f"s_addc_u32 s{S_CALL + 1}, s{S_CALL + 1}, {label_}@rel32@hi+12",
-            f"s_swappc_b64 s[{ret}:{ret + 1}], s[{S_CALL}:{S_CALL + 1}]"]
+    return s + call("lcb_r_fp2dw")
 
 
 # LDS quads of the three double-width diagonal products v_k = x_k y_k: re at 12k, im at 12k + 6
@@ -638,7 +444,7 @@ def fp6_finish(RE, IM, offs, nsub, out_a):
         s += mov_regs(F2_RE, RE)
     s += merge([movs_const(T2, pp_limbs(offs[0])), movs_const(T3, pp_limbs(offs[1]))])
     s += merge([add_chain(F2_RE, F2_RE, T2, LIN_CARRY[0]), add_chain(F2_IM, F2_IM, T3, LIN_CARRY[1])])
-    return s + call_redc2() + agpr_write(out_a, F2_RE[N:]) + agpr_write(out_a + 12, F2_IM[N:])
+    return s + call("lcb_r_redc2") + agpr_write(out_a, F2_RE[N:]) + agpr_write(out_a + 12, F2_IM[N:])
 
 
 def gen_fp6m():
@@ -684,16 +490,16 @@ def gen_fp12m():
     36 quads are overwritten).  Returns through s[30:31]; clobbers v0..v243, a144..a215."""
     X, Y, Z, W = T1[:12], T1[12:], T2[:12], T2[12:]
     b = movs_const(PR, PL) + [f"s_mov_b32 s{S_PINV}, 0x{PINV:08x}"]
-    b += [f"s_mov_b32 s{S_Q0}, 0", f"s_mov_b32 s{S_SUM}, 0"] + call_ret("lcb_r_fp6m", S_RET6)   # t0 = a0 m0
+    b += [f"s_mov_b32 s{S_Q0}, 0", f"s_mov_b32 s{S_SUM}, 0"] + call("lcb_r_fp6m", S_RET6)   # t0 = a0 m0
     b += ["s_nop 4"] + gstore(S_T, (None, 0), list(range(144, 216)), "a")
     for i in range(6):                                   # a[0:71] <- a1, a[72:143] <- s = a0 + a1
         b += agpr_read(X, 12 * i) + agpr_read(Y, 72 + 12 * i) + ["s_nop 1"]
         b += agpr_write(12 * i, Y) + modadd(X, X, Y, Z, LIN_CARRY[0]) + agpr_write(72 + 12 * i, X)
-    b += [f"s_mov_b32 s{S_Q0}, 18"] + call_ret("lcb_r_fp6m", S_RET6)                            # t1 = a1 m1
+    b += [f"s_mov_b32 s{S_Q0}, 18"] + call("lcb_r_fp6m", S_RET6)                            # t1 = a1 m1
     b += ["s_nop 4"] + gstore(S_T, (None, 18), list(range(144, 216)), "a")
     for i in range(6):                                   # a[0:71] <- s
         b += agpr_read(X, 72 + 12 * i) + ["s_nop 1"] + agpr_write(12 * i, X)
-    b += [f"s_mov_b32 s{S_Q0}, 0", f"s_mov_b32 s{S_SUM}, 1"] + call_ret("lcb_r_fp6m", S_RET6)   # t2 = s (m0 + m1)
+    b += [f"s_mov_b32 s{S_Q0}, 0", f"s_mov_b32 s{S_SUM}, 1"] + call("lcb_r_fp6m", S_RET6)   # t2 = s (m0 + m1)
     b += ["s_nop 4", "s_waitcnt vmcnt(0)"]
     # r1 = t2 - t0 - t1 -> a[72:143]
     for k in range(3):
@@ -752,7 +558,7 @@ def gen_fp12_mul_n():
     skip = label("mulnc")
     b = ["s_mov_b64 s[24:25], s[30:31]"] + walk_load(S_A)
     b += [f"s_cmp_eq_u32 s{S_CONJ}, 0", f"s_cbranch_scc1 {skip}"] + conj_c1() + [f"{skip}:", "s_nop 4"]
-    b += call_ret("lcb_r_fp12m", 30) + walk_store(S_DST) + ["s_setpc_b64 s[24:25]"]
+    b += call("lcb_r_fp12m", 30) + walk_store(S_DST) + ["s_setpc_b64 s[24:25]"]
     return ["lcb_r_fp12_mul_n:"] + hazard_fix(b)
 
 
@@ -764,10 +570,10 @@ def gen_pow_z():
     runs = [1, 2, 3, 9, 32, 16]
     for t, cnt in enumerate(runs):
         loop = label("pzrun")
-        b += [f"s_mov_b32 s18, {cnt}", f"{loop}:"] + call_ret("lcb_r_cyc_sqr", 30)
+        b += [f"s_mov_b32 s18, {cnt}", f"{loop}:"] + call("lcb_r_cyc_sqr", 30)
         b += ["s_sub_u32 s18, s18, 1", "s_cmp_lg_u32 s18, 0", f"s_cbranch_scc1 {loop}", "s_nop 4"]
         if t < len(runs) - 1:
-            b += call_ret("lcb_r_fp12m", 30) + ["s_nop 4"]
+            b += call("lcb_r_fp12m", 30) + ["s_nop 4"]
     b += conj_c1() + walk_store(S_DST) + ["s_setpc_b64 s[24:25]"]
     return ["lcb_r_pow_z:"] + hazard_fix(b)
 
@@ -788,11 +594,6 @@ LINE_B, LINE_C, LINE_BC = T1, T2, T3              # b, c, b + c (< p) across the
 K4PP = pp_limbs(4)
 
 
-def add_hi(U, f):
-    """U (24 words, mod 2^768) += f * 2^384"""
-    return add_chain(U[N:], U[N:], f, LIN_CARRY[2])
-
-
 def dw_park_a(abase, RE, IM):
     return agpr_write(abase, RE) + agpr_write(abase + 24, IM)
 
@@ -806,11 +607,7 @@ def redc_pair(RE, IM, nsub, out):
     assert RE == F2_RE and IM == F2_IM
     s = movs_const(list(range(0, 24)), K4PP)
     s += merge([add_chain(RE, RE, list(range(0, 24)), LIN_CARRY[0]), add_chain(IM, IM, list(range(0, 24)), LIN_CARRY[1])])
-    return s + call_redc2() + out(RE[N:], IM[N:])
-
-
-def mov_regs(dst, src):
-    return [f"v_mov_b32 v{d}, v{x}" for d, x in zip(dst, src)]
+    return s + call("lcb_r_redc2") + out(RE[N:], IM[N:])
 
 
 def xi_into(dst_a, dst_b, src_a, src_b, tmp):
@@ -858,14 +655,14 @@ def gen_line():
         b += gload(list(range(24, 36)), S_P, (S_PQ, 3 * half)) + ["s_waitcnt vmcnt(0)"]
         b += comba([dict(a=list(range(48, 60)), b=list(range(24, 36)), acc=F2_ACCS[0], out=F2_RE, c=MAD_CARRY[0]),
                     dict(a=list(range(60, 72)), b=list(range(24, 36)), acc=F2_ACCS[1], out=F2_IM, c=MAD_CARRY[1])])
-        b += call_redc2() + mov_regs(dst, F2_RE[N:] + F2_IM[N:])
+        b += call("lcb_r_redc2") + mov_regs(dst, F2_RE[N:] + F2_IM[N:])
     b += merge([modadd(LINE_BC[:12], LINE_B[:12], LINE_C[:12], list(range(0, 12)), LIN_CARRY[0]),
                 modadd(LINE_BC[12:], LINE_B[12:], LINE_C[12:], list(range(12, 24)), LIN_CARRY[1])])
     RE, IM = F2_RE, F2_IM
     T = list(range(0, 24)), list(range(24, 48))          # temps after a call (fp2dw inputs are dead)
 
     def call_xy(xregs, yprep):
-        return yprep + mov_regs(F2_XA + F2_XB, xregs) + call_fp2dw()
+        return yprep + mov_regs(F2_XA + F2_XB, xregs) + call("lcb_r_fp2dw")
 
     def sub_lds(q, c0, c1):                               # RE -= LDS[q..q+5], IM -= LDS[q+6..q+11]
         return (lds_read(T[0], q) + lds_read(T[1], q + 6) + ["s_waitcnt lgkmcnt(0)"] +
@@ -933,7 +730,7 @@ def gen_fp12sq():
     X, Y, Z, W = T1[:12], T1[12:], T2[:12], T2[12:]
     b = ["s_nop 4"] + gstore(S_T, (None, 0), list(range(0, 144)), "a") + ["s_waitcnt vmcnt(0)"]   # S1 = [a | b]
     b += [f"s_mov_b64 s[{S_M}:{S_M + 1}], s[{S_T}:{S_T + 1}]", f"s_mov_b32 s{S_Q0}, 18", f"s_mov_b32 s{S_SUM}, 0"]
-    b += call_ret("lcb_r_fp6m", S_RET6)                                              # t = a b -> a[144:215]
+    b += call("lcb_r_fp6m", S_RET6)                                              # t = a b -> a[144:215]
     b += ["s_nop 4"]
     # x = a + v b -> a[0:71]: (a0 + xi b2, a1 + b0, a2 + b1)
     b += agpr_read(X, 120) + agpr_read(Y, 132) + ["s_nop 1"] + xi_into(Z, W, X, Y, T3)          # xi b2
@@ -945,7 +742,7 @@ def gen_fp12sq():
     for i in range(6):                                                               # t -> a[72:143] (b consumed)
         b += agpr_read(X, 144 + 12 * i) + ["s_nop 1"] + agpr_write(72 + 12 * i, X)
     b += [f"s_mov_b32 s{S_Q0}, 0", f"s_mov_b32 s{S_SUM}, 1"]
-    b += call_ret("lcb_r_fp6m", S_RET6)                                              # u = x (a + b) -> a[144:215]
+    b += call("lcb_r_fp6m", S_RET6)                                              # u = x (a + b) -> a[144:215]
     b += ["s_nop 4"]
     # c0_k = u_k - t_k - (v t)_k with (v t)_0 = xi t_2, (v t)_1 = t_0, (v t)_2 = t_1; then c1 = 2t
     U3, U4 = T3[:12], T3[12:]
@@ -983,11 +780,11 @@ def gen_miller2():
             add_next = False
         else:
             if k > 0:
-                b += call_ret("lcb_r_fp12sq", 30)
+                b += call("lcb_r_fp12sq", 30)
             add_next = bool((Z_ABS_BITS >> i) & 1)
             i -= 1
         for t in range(2):
-            b += [f"s_mov_b32 s{S_SET}, {t}", f"s_mov_b32 s{S_PQ}, {6 * t}"] + call_ret("lcb_r_line", 30)
+            b += [f"s_mov_b32 s{S_SET}, {t}", f"s_mov_b32 s{S_PQ}, {6 * t}"] + call("lcb_r_line", 30)
             vp = V_LS[t]
             b += [f"v_add_co_u32_e64 v{vp}, {sp(LIN_CARRY[0])}, v{vp}, s{S_QT + 1}",
                   f"v_addc_co_u32_e64 v{vp + 1}, {sp(LIN_CARRY[0])}, v{vp + 1}, 0, {sp(LIN_CARRY[0])}", "s_nop 2"]
@@ -999,58 +796,34 @@ Z_ABS_BITS = 0xd201000000010000
 
 
 # ------------------------------------------------------------------ emit
-def clobbers_n():
-    regs = [f'"v{i}"' for i in range(VMAX)] + [f'"a{i}"' for i in range(A_PARK + 2 * N)]
-    regs += [f'"s{s}"' for s in CLOBBER_SGPRS + [16, 17, 24, 25]] + ['"scc"', '"vcc"']
-    return ", ".join(regs)
-
-
-def clobbers(nv=VMAX):
-    regs = [f'"v{i}"' for i in range(nv)] + [f'"a{A_PARK + j}"' for j in range(2 * N)]
-    regs += [f'"s{s}"' for s in CLOBBER_SGPRS] + ['"scc"', '"vcc"']
-    return ", ".join(regs)
+def wrapper_clobbers(n_agpr, sgprs):
+    """v0..v247, a0..a(n_agpr - 1), the routines' SGPRs and the wrapper's own (sgprs), scc, vcc"""
+    return clobbers(v=range(VMAX), a=range(n_agpr), s=sgprs, flags=["scc", "vcc"])
 
 
 def emit():
+    _lbl[0] = 0
     fp4_txt, fp4_outs, fp4_used = gen_fp4()
     cyc_txt = gen_cyc_sqr(fp4_outs, fp4_used)
     routines = [gen_cyc_sqr_n(), cyc_txt, fp4_txt, gen_pow_z(), gen_fp12_mul_n(), gen_fp12m(), gen_fp6m(),
                 gen_fp2dw(), gen_redc2(), gen_miller2(), gen_fp12sq(), gen_line()]
-    lib = "\n".join("  .p2align 8\n" + "\n".join(("  " + l) if not l.endswith(":") else l for l in r)
-                    for r in routines)
-    esc = lib.replace("\\", "\\\\").replace('"', '\\"')
-    o = []
-    o.append("// GENERATED by tools/gen_tower_asm.py — do not edit.\n")
-    o.append("// gfx950 Fp12-level assembly routines over an AGPR-resident accumulator (see the generator's docstring).\n")
-    o.append("#pragma once\n#include <hip/hip_runtime.h>\n#include <stdint.h>\n\n")
-    o.append("typedef uint32_t u32;\n\n")
-    o.append("#define LCB_ASM_TOWER_LIBRARY(tag) \\\n")
-    o.append("extern \"C\" __global__ void __launch_bounds__(64) lcb_asm_tower_library_##tag() { \\\n")
-    o.append("    asm volatile(LCB_ASM_TOWER_LIBRARY_TEXT); \\\n}\n\n")
-    o.append("#define LCB_ASM_TOWER_LIBRARY_TEXT \\\n    \"  s_endpgm\\n\" \\\n")
-    for line in esc.split("\n"):
-        o.append(f'    "{line}\\n" \\\n')
-    o.append('    ""\n\n')
+    o = [library_header("gen_tower_asm.py", "gfx950 Fp12-level assembly routines over an AGPR-resident accumulator "
+                        "(see the generator's docstring).", "typedef uint32_t u32;\n", "LCB_ASM_TOWER", routines)]
+    call_seq = lambda lbl: c_quote(call(lbl, 30))                                   # noqa: E731
+    clobbers_n = wrapper_clobbers(A_PARK + 2 * N, CLOBBER_SGPRS + [16, 17, 24, 25])
+    fp12_sgprs = set(CLOBBER_SGPRS) | {16, 17, 18, 24, 25, 62, 64, 66, 67, 68, 72, 73}
+    fp12_clob = wrapper_clobbers(216, sorted(fp12_sgprs))
+    ml_clob = wrapper_clobbers(240, sorted(fp12_sgprs | {20, 21, 63, 69}))
     o.append(f"""// slot_out <- slot_in^(2^count) for an Fp12 in the cyclotomic subgroup (count >= 1 Granger-Scott squarings in
 // AGPRs); slots are quad-major SoA (kcommon.hpp: word quad g of item i at byte (g * n + i) * 16), n16 = n * 16,
 // lane_off = i * 16.  Reads / writes memory; clobbers v0..v247, a0..a167.
 __device__ __forceinline__ void lcb_asm_cyc_sqr_n(const u32 *slot_in, u32 *slot_out, u32 n16, u32 lane_off, u32 count) {{
-    asm volatile("s_getpc_b64 s[{S_CALL}:{S_CALL + 1}]\\n\\t"
-        "s_add_u32 s{S_CALL}, s{S_CALL}, lcb_r_cyc_sqr_n@rel32@lo+4\\n\\t"
-        "s_addc_u32 s{S_CALL + 1}, s{S_CALL + 1}, lcb_r_cyc_sqr_n@rel32@hi+12\\n\\t"
-        "s_swappc_b64 s[30:31], s[{S_CALL}:{S_CALL + 1}]"
+    asm volatile({call_seq("lcb_r_cyc_sqr_n")}
         : "+{{s18}}"(count)
         : "{{s[20:21]}}"(slot_in), "{{s[22:23]}}"(slot_out), "{{s19}}"(n16), "{{v248}}"(lane_off)
-        : {clobbers_n()}, "memory");
+        : {clobbers_n}, "memory");
 }}
 """)
-    fp12_clob = ", ".join([f'"v{i}"' for i in range(VMAX)] + [f'"a{i}"' for i in range(216)] +
-                          [f'"s{x}"' for x in sorted(set(CLOBBER_SGPRS) | {16, 17, 18, 24, 25, 62, 64, 66, 67, 68,
-                                                                              72, 73})] + ['"scc"', '"vcc"'])
-    call_seq = lambda lbl: (f'"s_getpc_b64 s[{S_CALL}:{S_CALL + 1}]\\n\\t"\n'
-                            f'        "s_add_u32 s{S_CALL}, s{S_CALL}, {lbl}@rel32@lo+4\\n\\t"\n'
-                            f'        "s_addc_u32 s{S_CALL + 1}, s{S_CALL + 1}, {lbl}@rel32@hi+12\\n\\t"\n'
-                            f'        "s_swappc_b64 s[30:31], s[{S_CALL}:{S_CALL + 1}]"')
     o.append(f"""
 // dst <- (conj_a ? conj(a) : a) * m over Fp12 slots (lcb_r_fp12_mul_n: Karatsuba over lazily reduced Fp6 products,
 // the accumulator in AGPRs); tmp: a slot the call may overwrite (the destination or a, never m); lds_addr: this
@@ -1073,9 +846,6 @@ __device__ __forceinline__ void lcb_asm_pow_z(const u32 *base, u32 *tmp, u32 *ds
         : {fp12_clob}, "memory");
 }}
 """)
-    ml_clob = ", ".join([f'"v{i}"' for i in range(VMAX)] + [f'"a{i}"' for i in range(240)] +
-                        [f'"s{x}"' for x in sorted(set(CLOBBER_SGPRS) | {16, 17, 18, 20, 21, 24, 25, 62, 63, 64, 66,
-                                                                            67, 68, 69, 72, 73})] + ['"scc"', '"vcc"'])
     o.append(f"""// dst <- conj(prod_k l1_k(P1) l2_k(P2)), the 68 normalised lines of two line sets (pairing.hpp miller2_norm_lds,
 // the same residues): ls1 / ls2 the lane's line sets (68 x 48 words), pslot a slot holding P1 at quads 0..5 and P2
 // at quads 6..11 ((0, 0) for a point at infinity), s1 / s2 two tmp slots, lds_addr the lane's 36 LDS quads.
@@ -1090,6 +860,10 @@ __device__ __forceinline__ void lcb_asm_miller2(const u32 *ls1, const u32 *ls2, 
 }}
 """)
     return "".join(o), dict(fp4_outs=fp4_outs, fp4_used=len(fp4_used), n_cyc=len(cyc_txt), n_fp4=len(fp4_txt))
+
+
+def render():
+    return emit()[0]
 
 
 def main():
