@@ -756,6 +756,74 @@ int lcb_block_txs_verify_dev(uint8_t *accept, uint8_t *detail, uint8_t *root_ok,
 int lcb_ctx_tx_phase_ms(lcb_ctx *ctx, float ms[3]);
 int lcb_tx_phase_ms(float ms[3]);
 
+/* ------------------------------------------------------------------ state trie: node hashes, checks, roots
+   Block.Header.StateHash is the Keccak-256 of six trie roots (BlockchainSnapshot.cs:71-80); each root is the hash of a
+   32-way hash-array-mapped trie (Lachain.Storage/Trie/TrieHashMap.cs, LeafNode.cs, InternalNode.cs):
+     leaf     = Keccak-256(int32 LE KeyHash.Length || KeyHash || Value)
+     internal = Keccak-256(label_0 || child_0 || label_1 || child_1 ...), labels = the set bits of ChildrenMask in
+                ascending order, zipped with the child hashes: pairs as far as both last (IsConsistent hashes a node with
+                too few or too many child hashes the same way)
+   Kernels: k_trie.hip.  No reference vector pins a trie hash; these entry points are pinned by the literal restatement
+   tests/pyref/trie.py over a Keccak that the reference's vector pins.  Storage itself (RocksDB, node ids and versions,
+   caches) stays with the caller: only node and state hashing is provided.
+   Items are given as in lcb_keccak256_batch: item i is the bytes [off[i], off[i + 1]) of its array.  The host-pointer
+   forms check what they can read; the device-pointer forms trust the caller for the records and offsets (nodes 4-byte,
+   offset / reference / order arrays 8-byte aligned). */
+typedef struct {
+    uint32_t kind;              /* 0 leaf, 1 internal (NodeType's values) */
+    uint32_t mask;              /* internal: ChildrenMask */
+    uint32_t key_len;           /* leaf: KeyHash.Length; any value is legal, as in the reference */
+    uint32_t reserved;          /* 0 */
+} lcb_trie_node;                /* 16 bytes */
+/* (a) NodeStorage.IsConsistent, TrieHashMap.RecalculateHash / CheckAllNodeHashes, the LeafNode constructor and
+   InternalNode.UpdateHash for a batch.  A leaf's bytes are KeyHash || Value; an internal node's bytes are its child hashes,
+   32 bytes each, in label order.  out32[i] = the node's hash; accept[i] = (hash == expected32[i]).  out32, or expected32
+   and accept, may be null.  The host form fails (-1) for a kind above 1, a non-zero reserved, internal bytes that are no
+   multiple of 32 and a key_len beyond the item. */
+int lcb_trie_node_hash_batch(uint8_t *out32, uint8_t *accept, const lcb_trie_node *nodes, const uint8_t *data,
+                             const uint64_t *data_off, const uint8_t *expected32, size_t n);
+int lcb_ctx_trie_node_hash_dev(lcb_ctx *ctx, uint8_t *out32, uint8_t *accept, const lcb_trie_node *nodes,
+                               const uint8_t *data, const uint64_t *data_off, const uint8_t *expected32, size_t n,
+                               void *stream);
+int lcb_trie_node_hash_dev(uint8_t *out32, uint8_t *accept, const lcb_trie_node *nodes, const uint8_t *data,
+                           const uint64_t *data_off, const uint8_t *expected32, size_t n, void *stream);
+/* (b) TrieHashMap.InsertAllNodes, and the commit of a block's updates when hashing is deferred: every node of the batch
+   is hashed once, children before parents.  Leaf i has bytes data[data_off[i] .. data_off[i + 1]) and no children.
+   Internal node i has children child_ref[child_off[i] .. child_off[i + 1]) in label order, popcount(mask) of them: ref >= 0
+   is node ref of this batch (any array order; a child may have several parents), ref < 0 is literals32[~ref], the hash of
+   a clean subtree outside the batch.  hash_out32: n x 32 bytes.  The host form computes each node's height and launches
+   one pass per height; it fails (-1) for a reference out of range, a cycle and a child count other than popcount(mask).
+   The device forms take the level order from the caller: order (device, n node indices, level 0 first) and level_off
+   (HOST memory, n_levels + 1 entries into order); level l may reference nodes of lower levels only. */
+int lcb_trie_rehash_batch(uint8_t *hash_out32, const lcb_trie_node *nodes, const uint8_t *data, const uint64_t *data_off,
+                          const uint64_t *child_off, const int64_t *child_ref, const uint8_t *literals32, size_t n_literals,
+                          size_t n);
+int lcb_ctx_trie_rehash_dev(lcb_ctx *ctx, uint8_t *hash_out32, const lcb_trie_node *nodes, const uint8_t *data,
+                            const uint64_t *data_off, const uint64_t *child_off, const int64_t *child_ref,
+                            const uint8_t *literals32, const uint64_t *order, const uint64_t *level_off, size_t n_levels,
+                            size_t n, void *stream);
+int lcb_trie_rehash_dev(uint8_t *hash_out32, const lcb_trie_node *nodes, const uint8_t *data, const uint64_t *data_off,
+                        const uint64_t *child_off, const int64_t *child_ref, const uint8_t *literals32,
+                        const uint64_t *order, const uint64_t *level_off, size_t n_levels, size_t n, void *stream);
+/* (c) The root hashes of B tries given as key/value sets: trie b holds items trie_off[b] .. trie_off[b + 1] (trie_off runs
+   from 0 to the item count).  keys_hashed = 0: the key hash is the Keccak-256 of the key, computed on the device
+   (TrieHashMap.Hash); 1: the keys are 32-byte key hashes.  The trie the reference's folding rules keep (ModifyInternalNode,
+   SplitLeafNode) is canonical — a subtree with one key is that leaf, a prefix shared by two or more key hashes is an
+   internal node, single-child chain nodes included — so the root depends on the set alone and is built here by sorting.
+   roots32[b] = the root, status[b] = 1; an empty set gives the zero hash (GetHash's fallback) with status 1; a set on which
+   the reference throws (two equal key hashes; two key hashes that differ in bit 255 only) gives status 0 and a zero root,
+   and the other tries of the call are unaffected.  The construction runs on the device; the call reads one word (the
+   longest common prefix) back and therefore synchronises the stream once, the device forms included.  The built nodes
+   are not returned. */
+int lcb_trie_root_batch(uint8_t *roots32, uint8_t *status, const uint8_t *keys, const uint64_t *key_off,
+                        const uint8_t *values, const uint64_t *val_off, const uint64_t *trie_off, size_t B, int keys_hashed);
+int lcb_ctx_trie_root_dev(lcb_ctx *ctx, uint8_t *roots32, uint8_t *status, const uint8_t *keys, const uint64_t *key_off,
+                          const uint8_t *values, const uint64_t *val_off, const uint64_t *trie_off, size_t B, size_t n_items,
+                          int keys_hashed, void *stream);
+int lcb_trie_root_dev(uint8_t *roots32, uint8_t *status, const uint8_t *keys, const uint64_t *key_off, const uint8_t *values,
+                      const uint64_t *val_off, const uint64_t *trie_off, size_t B, size_t n_items, int keys_hashed,
+                      void *stream);
+
 /* ------------------------------------------------------------------ secp256k1 ECIES (the trustless DKG's envelopes)
    Every secret of the trustless key generation travels in DefaultCrypto.Secp256K1Encrypt and is opened by
    Secp256K1Decrypt (DefaultCrypto.cs:301-336): StartKeygen wraps one row per validator, HandleCommit opens a row and

@@ -202,6 +202,9 @@ struct lcb_ctx {
     DevBuf tx[13];
     hipEvent_t tx_ev[4] = {};         // around hashing / recovery and decision / roots of the last call
     bool tx_ev_ready = false, tx_ran = false;
+    // state trie (lcb_trie.cpp): [0] the flat call's list of internal nodes, [1] the root builder's workspace,
+    // [2..11] staging of the host-pointer forms
+    DevBuf trie[12];
 };
 
 // Enqueue scope: exclusive use of the context, stream ordered after the context's previous work, and the

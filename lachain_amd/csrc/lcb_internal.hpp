@@ -38,6 +38,7 @@ extern int g_orig_cofactor;           // lcb_set_original_g2_cofactor: the hashi
 void ecdsa_ctx_release(lcb_ctx *c);   // lcb_ecdsa.cpp: the context's cached key set
 void ecies_ctx_release(lcb_ctx *c);   // lcb_ecies.cpp: the envelope workspaces and events
 void txhash_ctx_release(lcb_ctx *c);  // lcb_txhash.cpp: the transaction workspaces and events
+void trie_ctx_release(lcb_ctx *c);    // lcb_trie.cpp: the state-trie workspaces
 
 // ---- lcb_host.cpp, for lcb_batch.cpp
 bool env_on(const char *name);              // an opt-in switch of the environment, read at call time

@@ -262,6 +262,13 @@ _SIGS = {
                                                                         ctypes.c_void_p, ctypes.c_void_p, c_size,
                                                                         ctypes.c_int, ctypes.c_int32, ctypes.c_void_p]),
     "lcb_tx_phase_ms": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float)]),
+    "lcb_trie_node_hash_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u64p, c_u8p, c_size]),
+    "lcb_trie_node_hash_dev": (ctypes.c_int, [ctypes.c_void_p] * 6 + [c_size, ctypes.c_void_p]),
+    "lcb_trie_rehash_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u64p, c_u64p, ctypes.POINTER(ctypes.c_int64), c_u8p,
+                                             c_size, c_size]),
+    "lcb_trie_rehash_dev": (ctypes.c_int, [ctypes.c_void_p] * 8 + [c_u64p, c_size, c_size, ctypes.c_void_p]),
+    "lcb_trie_root_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u64p, c_u8p, c_u64p, c_u64p, c_size, ctypes.c_int]),
+    "lcb_trie_root_dev": (ctypes.c_int, [ctypes.c_void_p] * 7 + [c_size, c_size, ctypes.c_int, ctypes.c_void_p]),
     "lcb_ctx_create": (ctypes.c_void_p, []),
     "lcb_ctx_destroy": (None, [ctypes.c_void_p]),
     "lcb_ctx_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
@@ -276,7 +283,8 @@ for _name in ("tpke_prepare_dev", "tpke_verify_prepared_dev", "tpke_verify_prepa
               "ecdsa_special_recover_hashed_dev", "tx_verify_dev", "ecdsa_recover_phase_ms", "keccak256_dev",
               "rbc_check_echo_dev", "rbc_merkle_tree_dev", "merkle_root_dev", "secp_ecdh_dev", "aes256_gcm_encrypt_dev",
               "aes256_gcm_decrypt_dev", "secp256k1_encrypt_dev", "secp256k1_decrypt_dev", "ecies_phase_ms", "tx_hash_dev",
-              "receipts_verify_dev", "block_txs_verify_dev", "tx_phase_ms"):
+              "receipts_verify_dev", "block_txs_verify_dev", "tx_phase_ms", "trie_node_hash_dev", "trie_rehash_dev",
+              "trie_root_dev"):
     _res, _args = _SIGS["lcb_" + _name]
     _SIGS["lcb_ctx_" + _name] = (_res, [ctypes.c_void_p] + list(_args))
 
@@ -1002,6 +1010,64 @@ def merkle_root_batch(trees):
     _check(lib().lcb_merkle_root_batch(pr, ps, ph, _u64_keep(keep, off), n), "merkle_root_batch")
     r = bytes(rb)
     return [r[32 * t:32 * t + 32] if sb[t] else None for t in range(n)]
+
+
+# ---------------------------------------------------------------- state trie
+TRIE_LEAF, TRIE_INTERNAL = 0, 1
+
+
+def trie_node(kind: int, mask: int = 0, key_len: int = 0) -> bytes:
+    """lcb_trie_node record (16 B): u32 kind | mask | key_len | 0"""
+    return struct.pack("<IIII", kind, mask, key_len, 0)
+
+
+def trie_node_hash_batch(records: bytes, items, expected: bytes = None):
+    """(hashes, accept) of n trie nodes: records are lcb_trie_node, items[i] a leaf's KeyHash || Value or an internal
+    node's child hashes back to back; accept is None without expected (n x 32 bytes)"""
+    n = len(items)
+    keep = []
+    _, pn = _bytes_ptr_keep(keep, records)
+    _, pd = _bytes_ptr_keep(keep, b"".join(items))
+    pe = None
+    if expected is not None:
+        _, pe = _bytes_ptr_keep(keep, expected)
+    hb, ph = _out(32 * n)
+    ab, pa = _out(n)
+    _check(lib().lcb_trie_node_hash_batch(ph, pa if expected is not None else None, pn, pd,
+                                          _u64_keep(keep, _offsets(items)), pe, n), "trie_node_hash_batch")
+    return bytes(hb)[: 32 * n], (bytes(ab)[:n] if expected is not None else None)
+
+
+def trie_rehash_batch(records: bytes, items, children, literals=()) -> bytes:
+    """hashes of n nodes, children before parents: children[i] is node i's reference list (>= 0: a node of the batch,
+    < 0: literals[~ref]), empty for a leaf"""
+    n = len(items)
+    keep = []
+    _, pn = _bytes_ptr_keep(keep, records)
+    _, pd = _bytes_ptr_keep(keep, b"".join(items))
+    _, pl = _bytes_ptr_keep(keep, b"".join(literals))
+    refs = [r for c in children for r in c]
+    ra = (ctypes.c_int64 * max(1, len(refs)))(*refs)
+    hb, ph = _out(32 * n)
+    _check(lib().lcb_trie_rehash_batch(ph, pn, pd, _u64_keep(keep, _offsets(items)), _u64_keep(keep, _offsets(children)),
+                                       ra, pl, len(literals), n), "trie_rehash_batch")
+    return bytes(hb)[: 32 * n]
+
+
+def trie_root_batch(tries, keys_hashed: bool):
+    """tries: a list of lists of (key, value).  Returns (roots, status): 32 bytes and one status byte per trie"""
+    B = len(tries)
+    items = [kv for t in tries for kv in t]
+    keep = []
+    _, pk = _bytes_ptr_keep(keep, b"".join(k for k, _ in items))
+    _, pv = _bytes_ptr_keep(keep, b"".join(v for _, v in items))
+    rb, pr = _out(32 * B)
+    sb, ps = _out(B)
+    _check(lib().lcb_trie_root_batch(pr, ps, pk, _u64_keep(keep, _offsets([k for k, _ in items])), pv,
+                                     _u64_keep(keep, _offsets([v for _, v in items])), _u64_keep(keep, _offsets(tries)), B,
+                                     int(bool(keys_hashed))), "trie_root_batch")
+    r = bytes(rb)
+    return [r[32 * b:32 * b + 32] for b in range(B)], bytes(sb)[:B]
 
 
 class EcdsaKeySet:
