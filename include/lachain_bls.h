@@ -417,6 +417,19 @@ int lcb_debug_coop_op(int op, const uint32_t *a, const uint32_t *b, size_t n, ui
    op & 255: 0 a b, 1 conj(a) b, 2 one Granger-Scott squaring, 3 a run of op >> 8 (1..255) squarings in one call,
    4 a^z (z < 0 the curve parameter; a unitary).  b is read by ops 0 and 1 only. */
 int lcb_debug_asm_tower(int op, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out);
+/* test hook: one routine of the secp256k1 device code on n (1..65536) arbitrary items, one lane each.  Words are
+   little-endian 32-bit limbs of 256-bit values; any value in [0, 2^256) is a legal field operand.
+   a and b, 25 words per item: x[8] y[8] z[8] inf.  A field or scalar operand is x; a point is Jacobian (x, y, z) with
+   inf != 0 for infinity; the affine operand of op 15 is (x, y) of b.  b may be null for operations of one operand.
+   out, 44 words per item: x[8] y[8] z[8] inf flags digits[18].
+   op 0..8: field mul, sqr, add, sub, neg, dbl, canon, inv (0 -> 0), sqrt (a^((p+1)/4)) -> x, weakly reduced except canon.
+   op 9: flags bit 0 a == 0, bit 1 a odd, bit 2 a == b (all mod p).
+   op 10: a b R^-1 mod n, op 11: (a R^-1)^-1 R mod n (R = 2^256; operands below n) -> x.
+   op 12: the endomorphism split of a and the signed 4-bit digits of both halves: magnitudes -> x, y; flags bit 0 / 1:
+   the first / second half is negative; digits: 36 signed bytes per half, low window first.
+   op 13: the comb's signed 8-bit digits of a -> digits, 36 signed bytes.
+   op 14: 2 a, op 15: a + affine b, op 16: a + b -> (x, y, z, inf); an infinite result has zero coordinates. */
+int lcb_debug_secp_op(int op, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out);
 /* test hook: lcb_tpke_verify_shares up to its Miller loop (the one-lane kernel) for n (1..65536) shares, without the
    final exponentiation: f_out = each share's Miller value (144 x u32), ok_out = its validity flag */
 int lcb_debug_tpke_miller(uint32_t *f_out, uint8_t *ok_out, size_t n, const uint8_t *y_keys, size_t n_keys,

@@ -318,6 +318,24 @@ extern "C" __global__ void __launch_bounds__(SECP_BLOCK) k_keccak256(const uint8
     for (int k = 0; k < 32; k++) out32[32 * (size_t)i + k] = (uint8_t)(s[k / 8] >> (8 * (k % 8)));
 }
 
+// ------------------------------------------------------------------------------------------------ test hook
+// one routine of secp.hpp / secp_comb.hpp / recode4 per lane on arbitrary operands (secp_debug.hpp has the layout)
+#include "secp_debug.hpp"
+extern "C" __global__ void __launch_bounds__(SECP_BLOCK) k_secp_debug(int op, const u32 *a, const u32 *b, u32 n,
+                                                                     u32 *out) {
+    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u32 ia[SECP_DEBUG_IN], ib[SECP_DEBUG_IN], o[SECP_DEBUG_OUT];
+#pragma unroll
+    for (int k = 0; k < SECP_DEBUG_IN; k++) {
+        ia[k] = a[(size_t)SECP_DEBUG_IN * i + k];
+        ib[k] = b[(size_t)SECP_DEBUG_IN * i + k];
+    }
+    secp_debug_op(op, ia, ib, o);
+#pragma unroll
+    for (int k = 0; k < SECP_DEBUG_OUT; k++) out[(size_t)SECP_DEBUG_OUT * i + k] = o[k];
+}
+
 #ifndef SECP_HOST_EMULATION
 // ---------------------------------------------------------------- host launch wrappers
 static unsigned rec_blocks_for(size_t n) { return (unsigned)((n + SECP_BLOCK - 1) / SECP_BLOCK); }
@@ -345,5 +363,12 @@ extern "C" void lcbk_secp_rec_finish(hipStream_t s, const void *pts, u32 n, uint
 extern "C" void lcbk_keccak256(hipStream_t s, const uint8_t *data, const uint64_t *off, u32 n, uint8_t *out32) {
     if (!n) return;
     LCB_LAUNCH_GATED(k_keccak256, dim3(rec_blocks_for(n)), dim3(SECP_BLOCK), 0, s, data, (const u64 *)off, n, out32);
+}
+extern "C" size_t lcbk_secp_debug_in_words(void) { return SECP_DEBUG_IN; }
+extern "C" size_t lcbk_secp_debug_out_words(void) { return SECP_DEBUG_OUT; }
+extern "C" int lcbk_secp_debug_ops(void) { return SECP_DEBUG_OPS; }
+extern "C" void lcbk_secp_debug(hipStream_t s, int op, const u32 *a, const u32 *b, u32 n, u32 *out) {
+    if (!n) return;
+    LCB_LAUNCH_GATED(k_secp_debug, dim3(rec_blocks_for(n)), dim3(SECP_BLOCK), 0, s, op, a, b, n, out);
 }
 #endif  // SECP_HOST_EMULATION

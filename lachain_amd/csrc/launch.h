@@ -102,6 +102,11 @@ extern "C" size_t lcbk_secp_rjob_bytes(void);
 extern "C" size_t lcbk_secp_rpoint_bytes(void);
 extern "C" void lcbk_secp_rec_scalars(hipStream_t s, const uint8_t *hashes, const uint8_t *sigs, u32 sig_len, u32 want_len, int chain_id, int special, u32 n, void *jobs);
 extern "C" void lcbk_secp_recover(hipStream_t s, const void *jobs, u32 n, const void *g_table, void *pts);
+// test hook (lcb_debug_secp_op): one secp256k1 routine per lane; items of lcbk_secp_debug_in_words() / _out_words() words
+extern "C" size_t lcbk_secp_debug_in_words(void);
+extern "C" size_t lcbk_secp_debug_out_words(void);
+extern "C" int lcbk_secp_debug_ops(void);
+extern "C" void lcbk_secp_debug(hipStream_t s, int op, const u32 *a, const u32 *b, u32 n, u32 *out);
 extern "C" void lcbk_secp_rec_finish(hipStream_t s, const void *pts, u32 n, uint8_t *pub33, uint8_t *addr20, uint8_t *ok, const uint8_t *from20, uint8_t *accept);
 extern "C" void lcbk_keccak256(hipStream_t s, const uint8_t *data, const uint64_t *off, u32 n, uint8_t *out32);
 extern "C" void lcbk_tx_hash(hipStream_t s, const uint8_t *txs, const uint8_t *inv, const uint64_t *off, const uint8_t *sigs, u32 sig_len, const uint8_t *claimed, u32 chain_id, u32 n, uint8_t *raw32, uint8_t *full32, uint8_t *match, uint32_t *long_ws);

@@ -553,3 +553,27 @@ extern "C" int lcb_keccak256_batch(uint8_t *out32, const uint8_t *data, const ui
     hipMemcpyAsync(out32, dout, 32 * n, hipMemcpyDeviceToHost, s);
     return sync_check(c, "keccak256") ? 0 : -1;
 }
+
+// ------------------------------------------------------------------ test hook
+// one routine of the secp256k1 device code (secp_debug.hpp: field, scalar, split / recoding and point operations) on
+// n items, one lane each (k_secp_debug).  a and b: 25 words per item, out: 44 words per item (include/lachain_bls.h);
+// b may be null for the operations of one operand
+extern "C" int lcb_debug_secp_op(int op, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out) {
+    SYNC_CTX_OR(c, -1)
+    if (!n || n > 65536) { set_err("debug secp op: 1..65536 items"); return -1; }
+    if (op < 0 || op >= lcbk_secp_debug_ops()) { set_err("debug secp op: unknown operation"); return -1; }
+    const bool binary = op == 0 || op == 2 || op == 3 || op == 9 || op == 10 || op == 15 || op == 16;
+    if (!a || !out || (binary && !b)) { set_err("debug secp op: missing operand"); return -1; }
+    const size_t in_w = lcbk_secp_debug_in_words() * n, out_w = lcbk_secp_debug_out_words() * n;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    Enq q(c, c->stream);
+    hipStream_t s = c->stream;
+    u32 *da = (u32 *)c->er[2].get(4 * in_w), *db = (u32 *)c->er[3].get(4 * in_w), *dout = (u32 *)c->er[5].get(4 * out_w);
+    if (!da || !db || !dout) { set_err("device allocation failed"); return -1; }
+    hipMemcpyAsync(da, a, 4 * in_w, hipMemcpyHostToDevice, s);
+    if (b) hipMemcpyAsync(db, b, 4 * in_w, hipMemcpyHostToDevice, s);
+    lcbk_secp_debug(s, op, da, b ? db : da, (u32)n, dout);
+    if (!launch_ok("debug secp op launch")) return -1;
+    hipMemcpyAsync(out, dout, 4 * out_w, hipMemcpyDeviceToHost, s);
+    return sync_check(c, "debug secp op") ? 0 : -1;
+}

@@ -116,6 +116,8 @@ _SIGS = {
                                            ctypes.c_int]),
     "lcb_debug_asm_tower": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_uint32),
                                            ctypes.POINTER(ctypes.c_uint32), c_size, ctypes.POINTER(ctypes.c_uint32)]),
+    "lcb_debug_secp_op": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_uint32),
+                                         ctypes.POINTER(ctypes.c_uint32), c_size, ctypes.POINTER(ctypes.c_uint32)]),
     "lcb_debug_tpke_miller": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32), c_u8p, c_size, c_u8p, c_size, c_u8p, c_u8p,
                                              c_u8p, c_u32p, c_size, c_u32p, c_u32p, c_u8p]),
     "lcb_batched_census": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32)]),
@@ -1409,6 +1411,23 @@ def debug_asm_tower(op, a_values, b_values=None, run=1):
     out = (ctypes.c_uint32 * (144 * n))()
     _check(lib().lcb_debug_asm_tower(code, a, b, n, out), "debug_asm_tower")
     return [list(out[144 * i:144 * i + 144]) for i in range(n)]
+
+
+SECP_DEBUG_OPS = {"mul": 0, "sqr": 1, "add": 2, "sub": 3, "neg": 4, "dbl": 5, "canon": 6, "inv": 7, "sqrt": 8, "pred": 9,
+                  "sc_mont_mul": 10, "sc_mont_inv": 11, "glv_split": 12, "comb_recode": 13, "jac_dbl": 14,
+                  "jac_add_aff": 15, "jac_add": 16}
+SECP_DEBUG_IN, SECP_DEBUG_OUT = 25, 44
+
+
+def debug_secp_op(op, a_items, b_items=None):
+    """one routine of the secp256k1 device code (lcb_debug_secp_op; op: a key of SECP_DEBUG_OPS) on items of 25 words
+    (x[8] y[8] z[8] inf) -> the 44-word results (x[8] y[8] z[8] inf flags digits[18]), include/lachain_bls.h"""
+    n = len(a_items)
+    a = (ctypes.c_uint32 * (SECP_DEBUG_IN * n))(*[w for v in a_items for w in v])
+    b = None if b_items is None else (ctypes.c_uint32 * (SECP_DEBUG_IN * n))(*[w for v in b_items for w in v])
+    out = (ctypes.c_uint32 * (SECP_DEBUG_OUT * n))()
+    _check(lib().lcb_debug_secp_op(SECP_DEBUG_OPS[op], a, b, n, out), "debug_secp_op")
+    return [list(out[SECP_DEBUG_OUT * i:SECP_DEBUG_OUT * (i + 1)]) for i in range(n)]
 
 
 def debug_tpke_miller(y_keys, cts, shares):

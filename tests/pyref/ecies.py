@@ -12,42 +12,10 @@ Where the reference throws, the functions here return None.
 """
 import hashlib
 
-P = 2 ** 256 - 2 ** 32 - 977
-N = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
-G = (0x79BE667EF9DCBBAC55A06295CE870B07029BFCDB2DCE28D959F2815B16F81798,
-     0x483ADA7726A3C4655DA4FBFC0E1108A8FD17B448A68554199C47D08FFB10D4B8)
+from .secp import G, N, P, compress, pt_add, pt_mul  # noqa: F401  (the affine group law lives in tests/pyref/secp.py)
 
 
 # ---------------------------------------------------------------- secp256k1, affine
-def pt_add(a, b):
-    if a is None:
-        return b
-    if b is None:
-        return a
-    if a[0] == b[0]:
-        if (a[1] + b[1]) % P == 0:
-            return None
-        lam = 3 * a[0] * a[0] * pow(2 * a[1], -1, P) % P
-    else:
-        lam = (b[1] - a[1]) * pow(b[0] - a[0], -1, P) % P
-    x = (lam * lam - a[0] - b[0]) % P
-    return x, (lam * (a[0] - x) - a[1]) % P
-
-
-def pt_mul(k, pt):
-    acc = None
-    while k:
-        if k & 1:
-            acc = pt_add(acc, pt)
-        pt = pt_add(pt, pt)
-        k >>= 1
-    return acc
-
-
-def compress(pt) -> bytes:
-    return bytes([2 | (pt[1] & 1)]) + pt[0].to_bytes(32, "big")
-
-
 def parse33(pub: bytes):
     """secp256k1_ec_pubkey_parse on a 33-byte slot: the point, or None"""
     if len(pub) != 33 or pub[0] not in (2, 3):

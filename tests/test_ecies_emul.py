@@ -63,6 +63,11 @@ def pools():
     ecdh = [(bytes.fromhex(e["pub"]), bytes.fromhex(e["scalar"])) for e in K["ecdh"]]
     ecdh += [(bad, keys[0]) for bad in _bad_keys(rng, pubs[1])] + [(pubs[1], d) for d in BAD_SCALARS]
     ecdh += [(pubs[i % 4], b32(rng.randrange(1, N))) for i in range(8)]
+    # recipient keys with the smallest x on the curve (1, 2, 3), both parities; a generator of their own, so that the
+    # other pools keep their inputs
+    erng = random.Random(0xEC1E5)
+    ecdh += [(bytes([pfx]) + b32(x), d) for x in (1, 2, 3) for pfx, d in ((2, b32(erng.randrange(1, N))), (3, b32(N - 1)))]
+    ecdh += [(b"\x02" + b32(1), b32(1)), (b"\x03" + b32(2), b32(2))]
     gcm_enc = [tuple(bytes.fromhex(g[k]) for k in ("key", "nonce", "pt")) for g in K["gcm"]]
     gcm_enc += [(rng.randbytes(32), rng.randbytes(16), rng.randbytes(ln)) for ln in GCM_LENGTHS[:9]]
     gcm_dec = [(bytes.fromhex(g["key"]), bytes.fromhex(g["out"])) for g in K["gcm"]]

@@ -13,12 +13,15 @@ import random
 import pytest
 
 import oracle as o
+import secp_cases
+from pyref import secp as S
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 K = json.load(open(os.path.join(HERE, "golden", "secp256k1_kats.json")))
 N, P = o.SECP_N, o.SECP_P
+EDGE_X = [x for xs in secp_cases.edge_xs() for x in xs]       # 1, 2, 3, 4, 6, 8, p - 3, p - 4, p - 10, ...
 
 
 @pytest.fixture(scope="module")
@@ -76,6 +79,10 @@ def _mixed_batch(rng, chain, new, n_keys=6, n=1500):
         bad_x += 1
     keys.append(b"\x02" + bad_x.to_bytes(32, "big"))  # x not on the curve
     keys.append(b"\x03" + P.to_bytes(32, "big"))      # x = p
+    # the points with the smallest and largest x on the curve (1, 2, 3, ..., p - 3, ...) as keys, both y each
+    n_plain = len(keys)
+    edge_pts = [pt for x in EDGE_X for pt in S.lift_x(x)]
+    keys += [S.compress(pt) for pt in edge_pts]
     hs, sigs, idx = [], [], []
     L = 66 if new else 65
     for i in range(n):
@@ -139,6 +146,20 @@ def _mixed_batch(rng, chain, new, n_keys=6, n=1500):
             keys.append(pk)
             j = len(keys) - 1
             sig = sig64 + tail
+        elif kind == 15:
+            # an edge-x key Q, whose private key nobody knows: R = a G + b Q, r = x(R), s = r / b, hash = a s verifies
+            # under Q by construction (the oracle decides).  Every third one carries an edge x as r instead.
+            e = (i // 16) % len(edge_pts)
+            j = n_plain + e
+            a, b = rng.randrange(1, N), rng.randrange(1, N)
+            rr = S.pt_add(S.pt_mul(a, S.G), S.pt_mul(b, edge_pts[e]))[0] % N
+            ss = rr * pow(b, -1, N) % N
+            if ss > N // 2:
+                ss, a = N - ss, N - a
+            h = (a * ss % N).to_bytes(32, "big")
+            if (i // 16) % 3 == 2:
+                rr = EDGE_X[(i // 48) % (len(EDGE_X) // 2)]
+            sig = rr.to_bytes(32, "big") + ss.to_bytes(32, "big") + tail
         hs.append(h)
         sigs.append(sig)
         idx.append(j)
@@ -251,6 +272,13 @@ def test_pubkey_and_sign_vs_oracle(nat):
     n = 300
     privs = [rng.randrange(1, N) for _ in range(n)]
     privs[0], privs[1], privs[2] = 0, N, N - 1                 # invalid, invalid, valid edge
+    # the smallest and largest keys, the endomorphism's eigenvalue, the halves' width, and every boundary of the comb's
+    # signed 8-bit windows: a digit of -128 with its carry, a run of 0xff digits that carries into the window above
+    lam, _ = secp_cases.glv()
+    edge = [1, 2, 3, N - 2, lam, 2 ** 128, 2 ** 128 - 1] + [0x80 << (8 * w) for w in range(32)] + \
+        [(1 << (8 * w)) - 1 for w in range(1, 32)] + [(0x7F << (8 * w)) | ((1 << (8 * w)) - 1) for w in range(1, 32)]
+    assert all(0 < e < N for e in edge) and 5 + len(edge) < n
+    privs[5:5 + len(edge)] = edge
     pb = b"".join(p.to_bytes(32, "big") for p in privs)
     keys, ok = nat.ecdsa_pubkey_batch(pb)
     for i, p in enumerate(privs):

@@ -67,6 +67,7 @@ BUDGET = {
     "k_rlc_miller_fallback": (0, 2376),
     "k_rlc_search": (106, 4056),              # round 5: baby-step giant-step (fingerprint table + the confirming power)
     "k_secp_scalars": (0, 528),
+    "k_secp_debug": (0, 0),                   # test hook: every secp256k1 routine behind one switch (secp_debug.hpp), 171 registers
     "k_tpke_ct_prepare": (0, 3800),
     "k_tpke_ct_prepare_h": (5, 4800),
     "k_tpke_ct_prepare_w": (5, 1208),

@@ -15,12 +15,14 @@ import subprocess
 import pytest
 
 import oracle as o
+import secp_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tools", "emul", "secp_recover_emul.cpp")
 LIB = os.path.join(ROOT, "tools", "emul", "libsecp_recover_emul.so")
 CSRC = os.path.join(ROOT, "lachain_amd", "csrc")
-DEPS = [SRC] + [os.path.join(CSRC, f) for f in ("k_secp_recover.hip", "k_secp.hip", "secp_comb.hpp", "secp.hpp")]
+DEPS = [SRC] + [os.path.join(CSRC, f) for f in ("k_secp_recover.hip", "k_secp.hip", "secp_comb.hpp", "secp.hpp",
+                                                 "secp_debug.hpp")]
 K = json.load(open(os.path.join(ROOT, "tests", "golden", "secp256k1_kats.json")))
 P, N = o.SECP_P, o.SECP_N
 KECCAK_LENGTHS = [0, 1, 55, 135, 136, 137, 271, 272, 273, 1000]
@@ -103,6 +105,7 @@ def v_bytes(rec: int, chain: int, new: bool, rng=None) -> bytes:
 _V_CACHE = {}
 SPLIT_T = [1, 2, N - 1, LAMBDA, N - LAMBDA, LAMBDA + 1, 2 ** 128 - 1, 2 ** 128]
 N_KINDS = 16
+EDGE_X = [x for xs in secp_cases.edge_xs() for x in xs]       # 1, 2, 3, 4, 6, 8, p - 3, p - 4, p - 10, ...
 
 
 def mixed_batch(rng, chain, new, n=1500):
@@ -187,6 +190,13 @@ def mixed_batch(rng, chain, new, n=1500):
         elif kind == 14:
             c, rid = signed(h, 1 if sub % 2 else N - 1)         # the keys G and -G
             sig = c + vb[rid]
+        elif kind == 15:
+            # x(R) is one of the smallest (1, 2, 3, ...) or largest (p - 3, ...) x on the curve, with either parity:
+            # as r itself, or as r + n through recovery ids 2 and 3 (every large one is above n)
+            x = EDGE_X[sub % len(EDGE_X)]
+            par = (sub // len(EDGE_X)) % 2
+            rr, rec = (x, par) if x < N else (x - N, 2 + par)
+            sig = rr.to_bytes(32, "big") + c[32:] + vb[rec]
         hs.append(h)
         sigs.append(sig)
         notes.append((kind, note))

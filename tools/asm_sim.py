@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """tools/asm_sim.py — single-lane interpreter for the generated gfx950 routine libraries (asm_routines.hpp,
-asm_tower.hpp).
+asm_tower.hpp) and for the inline blocks of secp_asm.hpp (tests/test_secp_asm_sim.py: VOP2 forms with their carries
+in VCC).
 
 Executes a library's text (the subset of VOP3 / SOP / global / LDS instructions the generators emit) for one lane
 with Python integers: registers, SCC, labels, branches, calls with a return stack, global memory (a dict of 32-bit
 words keyed by byte address) and LDS.  The generators' arithmetic and their register contract (which registers a
 routine may write) are checked with it on the CPU by tests/test_asm_routines.py and tests/test_asm_tower.py.
 """
+import functools
 import os
 import re
 
@@ -41,6 +43,7 @@ def load_library(path=HPP, macro="LCB_ASM_LIBRARY_TEXT"):
     return load_program(path, macro)
 
 
+@functools.lru_cache(maxsize=None)
 def _regs(op):
     """'v12' -> ('v', [12]); 'v[36:37]' -> ('v', [36, 37]); 's[90:91]' -> ('s', [90, 91])"""
     m = re.fullmatch(r"([vsa])(\d+)", op)
@@ -59,8 +62,13 @@ class ProgLane:
         self.written_v, self.written_s, self.written_a = set(), set(), set()
         self.counts = {}
         self.mem, self.lds, self.scc = {}, {}, 0
+        self.vcc, self.vcc_written = None, False      # this lane's bit of VCC (the inline blocks of secp_asm.hpp)
 
     def get(self, op):
+        if op == "vcc":
+            if self.vcc is None:
+                raise KeyError("read of undefined vcc")
+            return self.vcc
         kind, rr = _regs(op)
         if kind is None:
             return int(op, 0) & M32
@@ -76,6 +84,9 @@ class ProgLane:
         return self.get(op) & 1
 
     def put(self, op, val):
+        if op == "vcc":
+            self.vcc, self.vcc_written = val & 1, True
+            return
         kind, rr = _regs(op)
         f, w = {"v": (self.v, self.written_v), "s": (self.s, self.written_s), "a": (self.a, self.written_a)}[kind]
         if kind == "v" and len(rr) == 2 and rr[0] % 2:
@@ -104,6 +115,15 @@ def _split_off(op):
     return (m.group(1), int(m.group(2))) if m else (op, 0)
 
 
+def _vop2(mn, ops):
+    """the VOP2 (e32) encodings take their carries in VCC only and a VGPR as the second source"""
+    if mn.endswith("_e32") and "_co_" in mn:
+        if ops[1] != "vcc" or (len(ops) > 4 and ops[4] != "vcc"):
+            raise ValueError(f"{mn}: the e32 form carries through vcc only: {ops}")
+    if mn.endswith("_e32") and _regs(ops[-2 if len(ops) > 4 else -1])[0] != "v":
+        raise ValueError(f"{mn}: the second source of an e32 form is a VGPR: {ops}")
+
+
 def run_program(prog, labels, entry, lane, max_steps=50_000_000):
     """run from label `entry` until the `s_setpc_b64` that returns from it"""
     pc, stack, target = labels[entry], [], None
@@ -121,6 +141,22 @@ def run_program(prog, labels, entry, lane, max_steps=50_000_000):
         elif mn in ("v_sub_co_u32_e64", "v_subb_co_u32_e64"):
             r = g(ops[2]) - g(ops[3]) - (lane.getmask(ops[4]) if mn == "v_subb_co_u32_e64" else 0)
             lane.put(ops[0], r & M32); lane.put(ops[1], 1 if r < 0 else 0)
+        elif mn in ("v_add_co_u32_e32", "v_addc_co_u32_e32"):       # VOP2: carry out (and in) through VCC
+            _vop2(mn, ops)
+            r = g(ops[2]) + g(ops[3]) + (lane.getmask(ops[4]) if mn == "v_addc_co_u32_e32" else 0)
+            lane.put(ops[0], r & M32); lane.put(ops[1], r >> 32)
+        elif mn in ("v_sub_co_u32_e32", "v_subb_co_u32_e32"):
+            _vop2(mn, ops)
+            r = g(ops[2]) - g(ops[3]) - (lane.getmask(ops[4]) if mn == "v_subb_co_u32_e32" else 0)
+            lane.put(ops[0], r & M32); lane.put(ops[1], 1 if r < 0 else 0)
+        elif mn == "v_mul_hi_u32":
+            lane.put(ops[0], (g(ops[1]) * g(ops[2])) >> 32)
+        elif mn == "v_mad_u32_u24":                                  # 24-bit sources, 32-bit sum
+            lane.put(ops[0], ((g(ops[1]) & 0xFFFFFF) * (g(ops[2]) & 0xFFFFFF) + g(ops[3])) & M32)
+        elif mn in ("v_mul_u32_u24", "v_mul_u32_u24_e32"):
+            if mn.endswith("_e32"):
+                _vop2(mn, ops)
+            lane.put(ops[0], ((g(ops[1]) & 0xFFFFFF) * (g(ops[2]) & 0xFFFFFF)) & M32)
         elif mn == "v_cndmask_b32_e64":
             lane.put(ops[0], g(ops[2]) if lane.getmask(ops[3]) else g(ops[1]))
         elif mn == "v_mul_lo_u32":

@@ -86,6 +86,13 @@ unsigned long long emu_recover(uint8_t *pub33, uint8_t *addr20, uint8_t *ok, uin
     if (products3) { products3[0] = p1 - p0; products3[1] = p2 - p1; products3[2] = p3 - p2; }
     return p2 - p1;
 }
+// the test hook's routine switch (secp_debug.hpp) over n items, on the C++ field operations: the layout of
+// lcb_debug_secp_op; b may be null for the operations of one operand
+void emu_debug_secp_op(int op, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out) {
+    if (!b) b = a;
+    for (size_t i = 0; i < n; i++)
+        secp_debug_op(op, a + SECP_DEBUG_IN * i, b + SECP_DEBUG_IN * i, out + SECP_DEBUG_OUT * i);
+}
 void emu_keccak256(uint8_t *out32, const uint8_t *data, const uint64_t *off, uint32_t n) {
     run(n, [&] { k_keccak256(data, (const u64 *)off, n, out32); });
 }

@@ -11,8 +11,13 @@ by column, then the top word (< 2^34) folded once more by C = 2^32 + 977, and a 
 (the result is < 2^256, congruent mod p: "weakly reduced", the representation secp.hpp uses).  977 and 0 live in
 VGPRs (gfx9 VOP3 takes no literal operands, VOP2 needs a VGPR second source).
 
-Verified by tests/test_secp_emul.py on the CPU only through the C++ path; the asm is checked on the GPU by
-tests/test_gpu_ecdsa.py (every decision against the oracle) and by tools/emul/secp_stage_dump.hip diffs.
+Verified at the edge operands of tests/secp_cases.py (every class of the reduction's tail and of the second correction
+pass of the sum and the difference, which no ladder over random keys enters) in three places, each against Python
+integers: the committed text of all four blocks interpreted on the CPU by tools/asm_sim.py (tests/test_secp_asm_sim.py,
+which also holds every block to its outputs and clobbers), the C++ path the emulations compile instead
+(tests/test_secp_edges_emul.py; tests/test_secp_emul.py on random operands), and the assembly on the device through
+lcb_debug_secp_op (tests/test_gpu_secp_edges.py, word for word against the simulation).  The protocol tests
+(tests/test_gpu_ecdsa.py and its siblings: every decision against the oracle) run it as the kernels do.
 """
 import os
 import sys
