@@ -269,6 +269,16 @@ int lcb_set_lines_coop_max(int max_sets);
 /* 1 (default): the fused batched calls build the validators' fixed-base tables before forking the preparation streams;
    0: on the randomisation stream beside them.  Tuning hook: -1 unless LCB_ALLOW_TUNING=1. */
 int lcb_set_keys_first(int on);
+/* The batched TPKE check's exponents.  lcb_set_rlc_share_exponents(1): one independent exponent per share, drawn from
+   its index in the batch; 0 (default): one per position in a level-1 group, t[ct_idx & 3][pos], 128 per call.
+   lcb_set_rlc_lane_permutation(0): the randomisation's lanes take the shares in batch order; 1 (default): sorted by
+   exponent, so that a wave skips the ladder columns its one exponent does not need.  lcb_set_rlc_pos_table_min: with
+   position exponents, batches of at least this many shares per key read the keys' multiples from a table of 128 per key
+   (default 512; 0: always; UINT32_MAX: never).  The decisions are the same in every setting.  Tuning hooks: -1 unless
+   LCB_ALLOW_TUNING=1. */
+int lcb_set_rlc_share_exponents(int on);
+int lcb_set_rlc_lane_permutation(int on);
+int lcb_set_rlc_pos_table_min(uint32_t shares_per_key);
 
 /* Randomized batch form of lcb_tpke_verify_prepared_dev (same arguments, same workspace, same validity rules;
    replaces the per-share loop over TPKE/PublicKey.cs:88-92 driven from HoneyBadger.cs:211-212).  Shares are grouped

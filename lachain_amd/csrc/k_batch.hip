@@ -8,7 +8,18 @@
 // subgroup U_i / Y_i are covered.  H is in G2 by construction; W is checked (k_lineset_fill, lineset_in_g2) and a ciphertext with
 // W outside G2 gets exact per-share checks.  For secret random exponents s_i (2^64 values, none 0 mod r; rlc_scalar):
 // prod_i g_i^(s_i) == 1  <=>  e(sum s_i U_i, H) e(-sum s_i Y_i, W) == 1, and if some g_i != 1 the product is 1 with
-// probability <= 2^-64.  So one Miller pair + final exponentiation decides a whole group of shares of one ciphertext;
+// probability <= 2^-64.  The test needs, per checked equation, exponents that are uniform, independent of each other
+// and unknown to whoever made the shares; it does not need them to differ between equations.  So a share's exponent
+// is drawn by its place, not by its index: s_i = t[set][pos], pos = the share's position in its level-1 group (its
+// offset in its run of one ciphertext, modulo the cap of 32: distinct within a group), set = ciphertext index & 3, 128
+// exponents per call from the call's ChaCha20 key (drawn after the shares are fixed).  Every group, sub-group and
+// level-2 relation lives inside one level-1 group, so its exponents are independent as before; groups of different
+// sets may also share one final exponentiation (k_tpke.hip, pair stage).  Not by decryptor: dec_idx is caller data and
+// may repeat in a group, and (c, d, S + D), (c, d, S - D) under one exponent would cancel with certainty.  With one
+// exponent per (set, pos) a wave of the randomisation can hold one exponent (k_rlc_pos_scatter sorts the lanes) and
+// skip the ladder columns it does not need, and the key side s_i Y_d takes 128 n_keys values (k_rlc_pos_table).
+// lcb_set_rlc_share_exponents(1) restores one exponent per share.  
+// So one Miller pair + final exponentiation decides a whole group of shares of one ciphertext;
 // a group that fails is split and re-checked, down to single shares, where g_i^(s_i) == 1 <=> g_i == 1 (gcd(s_i, r)
 // = 1): every rejected share is rejected by an exact check of its own, every accepted share by a group check (false
 // accept <= 2^-64 per group, over the secret exponents).
@@ -21,9 +32,11 @@
 // s_i are secret), and the group's shares get single checks at the next level.  So at most three levels.
 //
 // Pipeline (host side in lcb_host.cpp: rlc_points_enqueue + rlc_levels):
-//   k_tpke_rlc_points   one lane per share: validity as k_tpke_miller, (a_i, b_i) = ChaCha20(key, i), s_i U_i and
-//                       s_i Y_i with s_i = a_i + b_i lambda (32-bit GLV form, rlc_scalar) -> quad-major SoA Jacobian
-//                       records (invalid share: infinity)
+//   k_rlc_pos_bins      the shares' bins (32 set + pos) and their histogram; k_rlc_pos_scatter: the shares sorted by bin
+//   k_rlc_pos_table     P[bin][d] = t[bin] Y_d, affine (batches that repay it; else the key's table per share)
+//   k_tpke_rlc_points   one lane per share, in bin order: validity as k_tpke_miller, (a, b) = ChaCha20(key, bin), s_i U_i
+//                       and s_i Y_i with s_i = a + b lambda (32-bit GLV form, rlc_scalar) -> quad-major SoA Jacobian
+//                       records at the share's index (invalid share: infinity)
 //   k_rlc_groups        one lane per 256 consecutive shares: runs of equal ciphertext index (<= 32) -> level-1 groups
 //   k_lineset_fill      (k_tpke.hip) W's line set also decides W in G2 (else its shares get exact per-share checks)
 //   k_tpke_rlc_sum      one lane per group: ciphertext validity, the two sums, to affine with one shared inversion,
@@ -75,6 +88,99 @@ extern "C" __global__ void LCB_BOUNDS k_rlc_groups(const u32 *key_idx, u32 i0, u
         u32 slot = atomicAdd(count, 1u);
         desc[slot] = make_uint4(st, len, c, 0);
     }
+}
+
+// ---------------------------------------------------------------- TPKE: positions, bins and the lane permutation
+// A share's exponent is t[set][pos] (header): pos = its offset in its run of equal ciphertext index modulo the group
+// cap (k_rlc_groups' run rule, so pos is its place in its level-1 group), set = the run's ciphertext & 3, bin =
+// 32 set + pos.  The randomisation handles the shares sorted by bin, so that the 64 lanes of a wave hold one exponent:
+// a counting sort over the 128 bins, all on the device.  Order inside a bin is free.
+//   k_rlc_pos_bins     the first share of a run walks it (as in k_rlc_groups): bin[i] for its shares, the run's counts
+//                      into the block's histogram, the block's into hist (zeroed by the caller)
+//   k_rlc_pos_scatter  start[b] = sum of hist below b; a block counts its chunk's bins, takes its places in every bin
+//                      with one atomic per bin on cursor (zeroed by the caller), then writes perm[place] = i
+// Both run over [i0, n) in chunks of `chunk` consecutive shares per block.
+extern "C" __global__ void LCB_BOUNDS k_rlc_pos_bins(const u32 *ct_idx, u32 i0, u32 n, u32 n_cts, u32 chunk,
+                                                    uint8_t *bin, u32 *hist) {
+    __shared__ u32 h[RLC_POS_BINS];
+    if (threadIdx.x < RLC_POS_BINS) h[threadIdx.x] = 0;
+    __syncthreads();
+    const u32 lo = i0 + min(n - i0, blockIdx.x * chunk), hi = lo + min(n - lo, chunk);
+    for (u32 i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+        u32 c = ct_idx[i];
+        c = c < n_cts ? c : 0;
+        if (i > i0) {
+            u32 p = ct_idx[i - 1];
+            p = p < n_cts ? p : 0;
+            if (p == c) continue;
+        }
+        const u32 b0 = (c & (RLC_POS_SETS - 1)) * RLC_POS_CAP;
+        u32 j = i;
+        do {                                       // (the run may leave the chunk: its first share owns all of it)
+            bin[j] = (uint8_t)(b0 + ((j - i) & (RLC_POS_CAP - 1)));
+            j++;
+            if (j >= n) break;
+            u32 q = ct_idx[j];
+            q = q < n_cts ? q : 0;
+            if (q != c) break;
+        } while (true);
+        const u32 len = j - i;
+        for (u32 p = 0; p < RLC_POS_CAP && p < len; p++)
+            atomicAdd(&h[b0 + p], (len - p + RLC_POS_CAP - 1) / RLC_POS_CAP);
+    }
+    __syncthreads();
+    if (threadIdx.x < RLC_POS_BINS && h[threadIdx.x]) atomicAdd(hist + threadIdx.x, h[threadIdx.x]);
+}
+extern "C" __global__ void LCB_BOUNDS k_rlc_pos_scatter(const uint8_t *bin, u32 i0, u32 n, u32 chunk, const u32 *hist,
+                                                       u32 *cursor, u32 *perm) {
+    __shared__ u32 cnt[RLC_POS_BINS], base[RLC_POS_BINS];
+    if (threadIdx.x < RLC_POS_BINS) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const u32 lo = i0 + min(n - i0, blockIdx.x * chunk), hi = lo + min(n - lo, chunk);
+    for (u32 i = lo + threadIdx.x; i < hi; i += blockDim.x) atomicAdd(&cnt[bin[i] & (RLC_POS_BINS - 1)], 1u);
+    __syncthreads();
+    if (threadIdx.x < RLC_POS_BINS) {
+        const u32 b = threadIdx.x, c = cnt[b];
+        u32 start = 0;
+        for (u32 k = 0; k < b; k++) start += hist[k];
+        base[b] = c ? start + atomicAdd(cursor + b, c) : 0;
+        cnt[b] = 0;
+    }
+    __syncthreads();
+    for (u32 i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+        const u32 b = bin[i] & (RLC_POS_BINS - 1);
+        const u32 t = base[b] + atomicAdd(&cnt[b], 1u);
+        if (t < n - i0) perm[t] = i;               // (always: the bins' counts add up to n - i0)
+    }
+}
+// P[bin][d] = t[bin] Y_d for the 128 bins and every key: affine x, y (24-word quad-major SoA records over the
+// 128 n_keys entries) and a flag (1: the point at infinity).  From the key's fixed-base table, or the ladder for a key
+// whose table is unusable; one binary-GCD inversion per entry.  The randomisation then copies a share's Y record from
+// P instead of forming it (the 22 keys are the same in every group): ~200 Fp products per entry, ~88 saved per share.
+extern "C" __global__ void LCB_BOUNDS k_rlc_pos_table(const g1a_st *keys, u32 n_keys, rlc_key key, const u32 *ktab,
+                                                     const uint8_t *ktab_ok, u32 *P, uint8_t *pinf) {
+    LCB_LATENCY_PRIO();
+    const u32 e = blockIdx.x * blockDim.x + threadIdx.x, ne = RLC_POS_BINS * n_keys;
+    if (e >= ne) return;
+    const u32 b = e / n_keys, d = e % n_keys;
+    u32 xa, xb;
+    rlc_scalar_dom(key, b, RLC_DOM_POS, xa, xb);
+    g1 q;
+    jac_set_inf(q);
+    if (ktab_usable(ktab_ok, d)) {
+        g1_mul_ab_tab(q, ktab, n_keys, d, xa, xb);
+    } else {
+        g1a_st ks = keys[d];
+        if (ks.ok) {                               // (a key that did not decode has no live share)
+            g1a Y;
+            st_to_g1a(Y, ks);
+            g1_mul_ab_n(q, Y, xa, xb);
+        }
+    }
+    g1a_st o;
+    g1_to_st_gcd(o, q, false);
+    soa_store<24>(P, ne, e, &o);                   // (x then y are the record's first 24 words)
+    pinf[e] = (uint8_t)o.inf;
 }
 
 // the weighted sums of the level-1 groups listed in sdesc (.w = level-1 group index) as affine records
@@ -467,6 +573,33 @@ extern "C" void lcbk_rlc_groups(hipStream_t s, const u32 *key_idx, u32 i0, u32 n
                                 u32 *count) {
     dim3 grid((n - i0 + LCB_BLOCK - 1) / LCB_BLOCK);
     LCB_LAUNCH(k_rlc_groups, key_idx, i0, n, n_keys, cap, (uint4 *)desc, count);
+}
+// positions of shares [i0, n): bin (one byte per share of the batch) and, with perm, the shares sorted by bin; bins:
+// 2 x RLC_POS_BINS words (histogram, cursors), zeroed here
+extern "C" size_t lcbk_rlc_pos_bins_bytes(void) { return 2 * RLC_POS_BINS * sizeof(u32); }
+extern "C" void lcbk_rlc_positions(hipStream_t s, const u32 *ct_idx, u32 i0, u32 n, u32 n_cts, uint8_t *bin, u32 *bins,
+                                   u32 *perm) {
+    if (n <= i0) return;
+    const u32 m = n - i0, nb = (u32)(((size_t)m + LCB_BLOCK - 1) / LCB_BLOCK), blocks = nb < 1024u ? nb : 1024u;
+    const u32 chunk = (u32)(((size_t)m + blocks - 1) / blocks);
+    (void)hipMemsetAsync(bins, 0, lcbk_rlc_pos_bins_bytes(), s);
+    dim3 grid(blocks);
+    LCB_LAUNCH(k_rlc_pos_bins, ct_idx, i0, n, n_cts, chunk, bin, bins);
+    if (perm) LCB_LAUNCH(k_rlc_pos_scatter, bin, i0, n, chunk, bins, bins + RLC_POS_BINS, perm);
+}
+// P and its flags in one allocation of lcbk_rlc_pos_table_bytes(n_keys)
+extern "C" size_t lcbk_rlc_pos_table_bytes(u32 n_keys) { return (size_t)RLC_POS_BINS * n_keys * (96 + 1) + 16; }
+extern "C" void lcbk_rlc_pos_table(hipStream_t s, const void *keys, u32 n_keys, const u32 key[10], const u32 *ktab,
+                                   const uint8_t *ktab_ok, u32 *ws, u32 **P, uint8_t **pinf) {
+    const size_t ne = (size_t)RLC_POS_BINS * n_keys;
+    rlc_key k;
+    for (int j = 0; j < 8; j++) k.k[j] = key[j];
+    k.nonce[0] = key[8];
+    k.nonce[1] = key[9];
+    *P = ws;
+    *pinf = (uint8_t *)(ws + 24 * ne);
+    dim3 grid((u32)((ne + LCB_BLOCK - 1) / LCB_BLOCK));
+    LCB_LAUNCH(k_rlc_pos_table, (const g1a_st *)keys, n_keys, k, ktab, ktab_ok, ws, *pinf);
 }
 extern "C" void lcbk_tpke_rlc_wsum(dim3 grid, hipStream_t s, const void *sdesc, u32 n_s, const u32 *wsum, u32 n_l1,
                                    void *gpts) {

@@ -69,13 +69,21 @@ extern "C" __global__ void LCB_BOUNDS k_rlc_key_tables(const g1a_st *keys, u32 n
 // the decompressed keys and may run beside the ciphertext preparation)
 // Shares [i0, n) (the census decides [0, i0) exactly); a share of a key the census has already marked suspect only
 // gets its validity (it is checked on its own).
+// Lane t handles share perm[t] (k_batch.hip k_rlc_pos_scatter: the shares sorted by bin, so a wave's lanes hold one
+// exponent and g1_mul_ab_wave skips the columns it does not need as a wave), or share i0 + t without perm.  bin: the
+// share's exponent is the bin's, t[bin] (position exponents); without it the share's own, from its index.  P / pinf
+// (with bin only): the share's Y record is P[bin][d] (k_rlc_pos_table).  Every record is stored at the share's index.
 extern "C" __global__ void __launch_bounds__(LCB_BLOCK) __attribute__((amdgpu_waves_per_eu(1)))
 k_tpke_rlc_points(u32 n_cts, const g1a_st *keys, u32 n_keys, const u32 *ct_idx,
                                                        const u32 *dec_idx, const uint8_t *ui, u32 i0, u32 n,
                                                        rlc_key key, u32 *rU, u32 *rY, uint8_t *accept,
-                                                       const u32 *ktab, const uint8_t *ktab_ok, const u32 *susp) {
-    u32 i = i0 + blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+                                                       const u32 *ktab, const uint8_t *ktab_ok, const u32 *susp,
+                                                       const u32 *perm, const uint8_t *bin, const u32 *P,
+                                                       const uint8_t *pinf) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n - i0) return;
+    u32 i = perm ? perm[t] : i0 + t;
+    if (i < i0 || i >= n) return;        // (never: perm is a permutation of [i0, n))
     u32 c = ct_idx[i], d = dec_idx[i];
     bool ok = d < n_keys && c < n_cts;
     g1a Ui, Y;
@@ -85,18 +93,30 @@ k_tpke_rlc_points(u32 n_cts, const g1a_st *keys, u32 n_keys, const u32 *ct_idx,
     st_to_g1a(Y, ks);
     if (ok && !key_suspect_live(susp, d, n_keys)) {
         u32 a, b;
-        rlc_scalar(key, i, a, b);
+        const u32 bn = bin ? bin[i] & (RLC_POS_BINS - 1) : 0;
+        if (bin) rlc_scalar_dom(key, bn, RLC_DOM_POS, a, b);
+        else rlc_scalar(key, i, a, b);
         // share side inlined (measured 144.7 vs 148.8 ms per 1M-share step with the call), key side from the key's
         // fixed-base table (148.8 vs 159.8 ms without).  Each record is stored as soon as it is formed (round 6): the
         // share side's point is then not live across the key side's call (its 36 words were the kernel's spills)
         {
             g1 p;
-            g1_mul_ab_inl(p, Ui, a, b);
+            g1_mul_ab_wave(p, Ui, a, b);
             g1_store_soa(rU, n, i, p);
         }
         g1 q;
-        if (ktab_usable(ktab_ok, d)) g1_mul_ab_tab(q, ktab, n_keys, d, a, b);
-        else g1_mul_ab_n(q, Y, a, b);
+        if (P) {
+            const size_t ne = (size_t)RLC_POS_BINS * n_keys, e = (size_t)bn * n_keys + d;
+            jac_set_inf(q);
+            if (!pinf[e]) {
+                soa_load<24>(&q, P, ne, e);          // (x then y are the record's first 24 words)
+                q.z = fp_one();
+            }
+        } else if (ktab_usable(ktab_ok, d)) {
+            g1_mul_ab_tab(q, ktab, n_keys, d, a, b);
+        } else {
+            g1_mul_ab_n(q, Y, a, b);
+        }
         g1_store_soa(rY, n, i, q);
     } else {                             // an invalid (or suspect) share contributes nothing to its group
         g1 p;
@@ -328,14 +348,15 @@ extern "C" void lcbk_rlc_key_tables(dim3 grid, hipStream_t s, const void *keys, 
 extern "C" void lcbk_tpke_rlc_points(hipStream_t s, u32 n_cts, const void *keys, u32 n_keys, const u32 *ct_idx,
                                      const u32 *dec_idx, const uint8_t *ui, u32 i0, u32 n, const u32 key[10], u32 *rU,
                                      u32 *rY, uint8_t *accept, const u32 *ktab, const uint8_t *ktab_ok,
-                                     const u32 *susp) {
+                                     const u32 *susp, const u32 *perm, const uint8_t *bin, const u32 *P,
+                                     const uint8_t *pinf) {
     rlc_key k;
     for (int j = 0; j < 8; j++) k.k[j] = key[j];
     k.nonce[0] = key[8];
     k.nonce[1] = key[9];
     dim3 grid((n - i0 + LCB_BLOCK - 1) / LCB_BLOCK);
     LCB_LAUNCH(k_tpke_rlc_points, n_cts, (const g1a_st *)keys, n_keys, ct_idx, dec_idx, ui, i0, n, k, rU, rY, accept,
-               ktab, ktab_ok, susp);
+               ktab, ktab_ok, susp, perm, bin, bin ? P : nullptr, pinf);
 }
 extern "C" void lcbk_tpke_rlc_sum(dim3 grid, hipStream_t s, const void *desc, u32 n_groups, u32 lanes,
                                   const uint8_t *ct_ok, const uint8_t *ct_g2, const void *keys, u32 n_keys,

@@ -376,23 +376,31 @@ extern "C" void lcbk_tpke_rlc_search2b_asm(hipStream_t s, const void *search, u3
 // homomorphism and every share's exponent is secret and independent, so FE(f_a f_b) = 1 accepts groups a and b
 // together (k_batch.hip header: a bad group passes only if gamma_a gamma_b = 1, one value of one exponent).  Job j of a
 // chunk of m entries covers entries a = 2j and b = 2j + 1, and holds one slot of the pair park (stride J = jobs):
-//   kind 0  both randomized groups (desc.w == 0): the slot takes f_a f_b.  If its final exponentiation is not 1, pass 2
+//   kind 0  both randomized groups (desc.w == 0) of different exponent sets (by_set; below): the slot takes f_a f_b.  If its final exponentiation is not 1, pass 2
 //           exponentiates f_a alone and gamma_b = gamma_ab conj(gamma_a) (the values are unitary after the easy part).
-//   kind 1  an exact single (desc.w == 1) among the two: no product.  The slot takes f_b, pass 2 always takes f_a, so
+//   kind 1  an exact single (desc.w == 1) among the two, or two groups of one set: no product.  The slot takes f_b, pass 2 always takes f_a, so
 //           each keeps an exponentiation of its own.
 //   kind 2  the odd last entry: the slot takes f_a.
+// by_set (TPKE position exponents, k_batch.hip header): a group of ciphertext c draws its shares' exponents from set
+// c & 3, so two groups of one set share their exponents and their product's would not be independent; they keep an
+// exponentiation each, like an exact single.  Groups of different sets use disjoint exponents and the sentence above
+// holds word for word.  (Consecutive ciphertexts differ in set, so nearly every neighbouring pair is formed.)
 // Every product runs on lcb_asm_fp12_mul_n over park slots, on canonical values, so gamma_b has the words a direct
 // exponentiation of f_b gives.  The call is per wave: the lanes past the last job have left (as in k_final_exp_check),
 // the lanes of a wave without a product of their own multiply by one, and a wave with no product at all (a level of
 // exact singles) copies its values instead.
 extern "C" __global__ void __launch_bounds__(64) k_fe_pair_pack(const uint4 *desc, const u32 *f, u32 m, u32 *park,
-                                                               u32 jobs, uint8_t *kind, uint8_t *pacc) {
+                                                               u32 jobs, uint8_t *kind, uint8_t *pacc, u32 by_set) {
     __shared__ uint4 lds[36 * 64];
     LCB_LATENCY_PRIO();
     const u32 j = blockIdx.x * 64 + threadIdx.x;
     if (j >= jobs) return;
     const u32 a = 2 * j, b = 2 * j + 1;
-    const u32 k = b >= m ? 2u : (desc[a].w == 0 && desc[b].w == 0) ? 0u : 1u;
+    u32 k = 2u;
+    if (b < m) {
+        const uint4 da = desc[a], db = desc[b];
+        k = (da.w == 0 && db.w == 0 && !(by_set && ((da.z ^ db.z) & 3u) == 0)) ? 0u : 1u;
+    }
     u32 *S0 = park, *S1 = park + (size_t)144 * jobs, *S2 = park + (size_t)288 * jobs;
     fp12 t;
     if (__ballot(k == 0) != 0) {         // (wave-uniform)
@@ -476,9 +484,9 @@ extern "C" __global__ void __launch_bounds__(64) k_fe_pair_finish(u32 *f, u32 m,
     }
 }
 extern "C" void lcbk_fe_pair_pack(hipStream_t s, const void *desc, const u32 *f, u32 m, u32 *park, u32 jobs,
-                                  uint8_t *kind, uint8_t *pacc) {
+                                  uint8_t *kind, uint8_t *pacc, u32 by_set) {
     LCB_LAUNCH_GATED(k_fe_pair_pack, dim3((jobs + 63) / 64), dim3(64), 0, s, (const uint4 *)desc, f, m, park, jobs,
-                     kind, pacc);
+                     kind, pacc, by_set);
 }
 extern "C" void lcbk_fe_pair_list(hipStream_t s, const uint8_t *kind, const uint8_t *pacc, u32 jobs, u32 *list,
                                   u32 *p2idx, u32 *cnt) {

@@ -126,7 +126,11 @@ extern "C" void lcbk_gcm_encrypt(hipStream_t s, const uint8_t *keys32, const uin
 extern "C" void lcbk_gcm_decrypt(hipStream_t s, const uint8_t *keys32, const uint8_t *ct, const uint64_t *ct_off, const uint64_t *out_off, u32 n, u32 hdr, uint8_t *pt_out, uint8_t *ok_out, const uint8_t *ok_in);
 extern "C" size_t lcbk_key_table_bytes(u32 n_keys);
 extern "C" void lcbk_rlc_key_tables(dim3 grid, hipStream_t s, const void *keys, u32 n_keys, u32 *ws, u32 **tab, uint8_t **ktab_ok);
-extern "C" void lcbk_tpke_rlc_points(hipStream_t s, u32 n_cts, const void *keys, u32 n_keys, const u32 *ct_idx, const u32 *dec_idx, const uint8_t *ui, u32 i0, u32 n, const u32 key[10], u32 *rU, u32 *rY, uint8_t *accept, const u32 *ktab, const uint8_t *ktab_ok, const u32 *susp);
+extern "C" void lcbk_tpke_rlc_points(hipStream_t s, u32 n_cts, const void *keys, u32 n_keys, const u32 *ct_idx, const u32 *dec_idx, const uint8_t *ui, u32 i0, u32 n, const u32 key[10], u32 *rU, u32 *rY, uint8_t *accept, const u32 *ktab, const uint8_t *ktab_ok, const u32 *susp, const u32 *perm, const uint8_t *bin, const u32 *P, const uint8_t *pinf);
+extern "C" size_t lcbk_rlc_pos_bins_bytes(void);
+extern "C" void lcbk_rlc_positions(hipStream_t s, const u32 *ct_idx, u32 i0, u32 n, u32 n_cts, uint8_t *bin, u32 *bins, u32 *perm);
+extern "C" size_t lcbk_rlc_pos_table_bytes(u32 n_keys);
+extern "C" void lcbk_rlc_pos_table(hipStream_t s, const void *keys, u32 n_keys, const u32 key[10], const u32 *ktab, const uint8_t *ktab_ok, u32 *ws, u32 **P, uint8_t **pinf);
 extern "C" void lcbk_ts_rlc_points(hipStream_t s, u32 n_msgs, const void *pks, u32 n_pks, const u32 *msg_idx, const u32 *pk_idx, const uint8_t *sigs, u32 i0, u32 n, const u32 key[10], u32 *rP, u32 *rS, uint8_t *accept, void *desc, u32 *count, const u32 *ktab, const uint8_t *ktab_ok, const u32 *susp, void *dec);
 extern "C" void lcbk_rlc_groups(hipStream_t s, const u32 *key_idx, u32 i0, u32 n, u32 n_keys, u32 cap, void *desc, u32 *count);
 extern "C" void lcbk_tpke_rlc_sum(dim3 grid, hipStream_t s, const void *desc, u32 n_groups, u32 lanes, const uint8_t *ct_ok, const uint8_t *ct_g2, const void *keys, u32 n_keys, const u32 *dec_idx, const uint8_t *ui, const u32 *rU, const u32 *rY, u32 n, void *gpts, uint8_t *accept, uint8_t *gexact, u32 *wsum, const u32 *susp, uint8_t *cval);
@@ -146,7 +150,7 @@ extern "C" void lcbk_tpke_rlc_search2b_asm(hipStream_t s, const void *search, u3
 extern "C" size_t lcbk_tpke_rlc_search2b_asm_park_bytes(u32 n_open);
 // level-1 pair stage (k_tpke.hip; host side lcb_host.cpp rlc_fe_pairs, switched by lcb_set_fe_pair_min and counted by
 // lcb_ctx_tpke_fe_pair_stats): jobs = ceil(m / 2) slots of the pair park, n2 = the jobs listed for pass 2
-extern "C" void lcbk_fe_pair_pack(hipStream_t s, const void *desc, const u32 *f, u32 m, u32 *park, u32 jobs, uint8_t *kind, uint8_t *pacc);
+extern "C" void lcbk_fe_pair_pack(hipStream_t s, const void *desc, const u32 *f, u32 m, u32 *park, u32 jobs, uint8_t *kind, uint8_t *pacc, u32 by_set);
 extern "C" void lcbk_fe_pair_list(hipStream_t s, const uint8_t *kind, const uint8_t *pacc, u32 jobs, u32 *list, u32 *p2idx, u32 *cnt);
 extern "C" void lcbk_fe_pair_gather(hipStream_t s, const u32 *f, u32 m, const u32 *list, u32 n2, u32 *park2, uint8_t *pacc2);
 extern "C" void lcbk_fe_pair_finish(hipStream_t s, u32 *f, u32 m, u32 *park, u32 jobs, const uint8_t *kind, const uint8_t *pacc, const u32 *p2idx, const u32 *park2, u32 n2, uint8_t *gacc);

@@ -23,6 +23,7 @@
 
 using namespace lcb_int;
 
+#define LCB_RLC_GROUP_CAP 32                  // shares per TPKE level-1 group (k_rlc_groups)
 #define LCB_VERIFY_CHUNK (c->chunk)             // lcb_set_verify_chunk's value for this call (lcb_ctx.hpp Enq)
 // level-2 two-error search on the assembly Fp12 products (k_tpke.hip k_tpke_rlc_search2b_asm, round 6)
 #ifndef LCB_SEARCH2B_ASM
@@ -190,19 +191,58 @@ u32 *rlc_key_tables(lcb_ctx *c, const void *keys, size_t n_keys, hipStream_t s, 
     lcbk_rlc_key_tables(dim3(1), s, keys, (u32)n_keys, ws, &tab, ktab_ok);
     return tab;
 }
+// The TPKE exponents (k_batch.hip header).  lcb_set_rlc_share_exponents(1): one exponent per share, from
+// its index (the form before the position exponents); 0 (default): per group position, t[set][pos].
+// lcb_set_rlc_lane_permutation(0): lane t of the randomisation handles share m + t; 1 (default): the shares sorted by
+// bin, so that a wave holds one exponent and skips its zero columns as a wave.  Each half can be measured alone.
+// (LCB_RLC_SHARE_EXP, LCB_RLC_LANE_PERM and LCB_RLC_POS_TABLE_MIN, with LCB_ALLOW_TUNING=1, set the starting values: A/B
+// runs of programs that do not call the setters)
+long tuning_env(const char *name, long dflt) {
+    const char *e = getenv(name);
+    return (e && *e && env_on("LCB_ALLOW_TUNING")) ? atol(e) : dflt;
+}
+std::atomic<int> g_share_exp{tuning_env("LCB_RLC_SHARE_EXP", 0) ? 1 : 0};
+std::atomic<int> g_lane_perm{tuning_env("LCB_RLC_LANE_PERM", 1) ? 1 : 0};
+// P = t[bin] Y_d for 128 bins x n_keys keys replaces the key side's eight table additions per share: an entry costs
+// about 200 Fp products (eight mixed additions and one inversion), 25,600 per key; a share saves about 88, so the
+// table repays itself from 291 shares per key.  512 leaves room for the table's latency ahead of the randomisation
+// (a launch of 2 n_keys waves).  lcb_set_rlc_pos_table_min overrides the figure (UINT32_MAX: never).
+#ifndef LCB_POS_TABLE_MIN
+#define LCB_POS_TABLE_MIN 512u
+#endif
+std::atomic<uint32_t> g_pos_table_min{(uint32_t)tuning_env("LCB_RLC_POS_TABLE_MIN", LCB_POS_TABLE_MIN)};
 // phase 1 (needs the decompressed keys only): per-share exponent multiples of shares [m, n) + level-1 groups (count
 // left on device in the CNT_GROUPS word)
 int rlc_points_enqueue(lcb_ctx *c, RlcWs &w, uint8_t *d_accept, size_t n, size_t n_keys, size_t n_cts,
                        const uint32_t *d_ct, const uint32_t *d_dec, const uint8_t *d_ui, hipStream_t s) {
     u32 key[10];
     if (!rlc_key_fill(c, key)) return -1;
+    const bool pos = !g_share_exp.load(), permute = g_lane_perm.load() != 0;
+    c->rlc_pos_exp = pos;
     hipEventRecord(c->rlc_ev[0], s);
     if (w.m < n) {
         uint8_t *kok = w.kok;
         u32 *ktab = w.ktab_pre ? w.ktab : rlc_key_tables(c, c->t_keys.p, n_keys, s, &kok);
+        // positions -> bins -> the lane permutation, and the keys' multiples per bin: all on this stream, no host read
+        uint8_t *bin = nullptr, *pinf = nullptr;
+        u32 *perm = nullptr, *P = nullptr;
+        if (pos || permute) {
+            bin = (uint8_t *)c->rlc[RLC_POS_BIN].get(n);
+            u32 *bins = (u32 *)c->rlc[RLC_POS_BINS].get(lcbk_rlc_pos_bins_bytes());
+            if (permute) perm = (u32 *)c->rlc[RLC_POS_PERM].get(4 * (n - w.m));
+            if (!bin || !bins || (permute && !perm)) { set_err("device allocation failed (positions)"); return -1; }
+            lcbk_rlc_positions(s, d_ct, w.m, (u32)n, (u32)n_cts, bin, bins, perm);
+        }
+        const uint32_t tmin = g_pos_table_min.load();
+        if (pos && ktab && tmin != UINT32_MAX && n - w.m >= (size_t)tmin * n_keys) {
+            u32 *pws = (u32 *)c->rlc[RLC_POS_TABLE].get(lcbk_rlc_pos_table_bytes((u32)n_keys));
+            if (!pws) { set_err("device allocation failed (position table)"); return -1; }
+            lcbk_rlc_pos_table(s, c->t_keys.p, (u32)n_keys, key, ktab, kok, pws, &P, &pinf);
+        }
         lcbk_tpke_rlc_points(s, (u32)n_cts, c->t_keys.p, (u32)n_keys, d_ct, d_dec, d_ui, w.m, (u32)n, key, w.rA, w.rB,
-                             d_accept, ktab, kok, w.susp);
-        lcbk_rlc_groups(s, d_ct, w.m, (u32)n, (u32)n_cts, 32, w.dA, w.cnt + CNT_GROUPS);
+                             d_accept, ktab, kok, w.susp, perm, pos ? bin : nullptr, P, pinf);
+        static_assert(LCB_RLC_GROUP_CAP == 32, "the position bins hold the level-1 groups' cap (rlc_common.hpp RLC_POS_CAP)");
+        lcbk_rlc_groups(s, d_ct, w.m, (u32)n, (u32)n_cts, LCB_RLC_GROUP_CAP, w.dA, w.cnt + CNT_GROUPS);
     }
     hipEventRecord(c->rlc_ev[1], s);
     return launch_ok("tpke batched verify launch") ? 0 : -1;
@@ -378,7 +418,7 @@ bool rlc_fe_pairs(lcb_ctx *c, const uint8_t *desc, u32 *f, u32 m, uint8_t *gacc,
     u32 *park2 = park + park_words;
     const FePairWs ws(lists, jobs);
     hipMemsetAsync(ws.cnt, 0, 16, s);
-    lcbk_fe_pair_pack(s, desc, f, m, park, jobs, ws.kind, ws.pacc);
+    lcbk_fe_pair_pack(s, desc, f, m, park, jobs, ws.kind, ws.pacc, c->rlc_pos_exp ? 1u : 0u);
     fe_dispatch(c, s, park, jobs, ws.pacc, true);
     lcbk_fe_pair_list(s, ws.kind, ws.pacc, jobs, ws.list, ws.p2idx, ws.cnt);
     enum { H_PASS2, H_FORMED, H_FAILED, H_N };    // the counters read back
@@ -1031,6 +1071,21 @@ extern "C" int lcb_set_level_mode(int mode) {
 extern "C" int lcb_set_fork_mode(int mode) {
     if (!tuning_allowed("lcb_set_fork_mode")) return -1;
     g_fork_mode.store(mode >= 1 && mode <= 4 ? mode : 0);
+    return 0;
+}
+extern "C" int lcb_set_rlc_share_exponents(int on) {
+    if (!tuning_allowed("lcb_set_rlc_share_exponents")) return -1;
+    g_share_exp.store(on ? 1 : 0);
+    return 0;
+}
+extern "C" int lcb_set_rlc_lane_permutation(int on) {
+    if (!tuning_allowed("lcb_set_rlc_lane_permutation")) return -1;
+    g_lane_perm.store(on ? 1 : 0);
+    return 0;
+}
+extern "C" int lcb_set_rlc_pos_table_min(uint32_t shares_per_key) {
+    if (!tuning_allowed("lcb_set_rlc_pos_table_min")) return -1;
+    g_pos_table_min.store(shares_per_key);
     return 0;
 }
 extern "C" int lcb_set_keys_first(int on) {

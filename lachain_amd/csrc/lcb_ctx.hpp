@@ -58,6 +58,10 @@ enum RlcBuf {
     RLC_S2B_PARK,     // the two-error search's Fp12 slots (lcbk_tpke_rlc_search2b_asm_park_bytes); rlc_levels
     RLC_PAIR_PARK,    // the level-1 pair stage's two park buffers (products + solos, then pass 2); rlc_fe_pairs
     RLC_PAIR_LISTS,   // its job lists (FePairWs); rlc_fe_pairs
+    RLC_POS_BIN,      // TPKE: per share, its exponent's bin (32 set + pos), one byte; rlc_points_enqueue
+    RLC_POS_PERM,     // TPKE: the shares behind the census sorted by bin, 4 B each; the same
+    RLC_POS_BINS,     // TPKE: the counting sort's histogram and cursors (lcbk_rlc_pos_bins_bytes); the same
+    RLC_POS_TABLE,    // TPKE: P[bin][key] = t[bin] Y_key and its flags (lcbk_rlc_pos_table_bytes); the same
     RLC_N
 };
 // The words of the device counter block RLC_CNT (the kernels take pointers to single words)
@@ -151,6 +155,7 @@ struct lcb_ctx {
     DevBuf rlc[RLC_N];
     uint32_t fe_pair[FE_PAIR_N] = {};         // last call's pair stage
     uint32_t lvl_kernel[LVL_KERNEL_N] = {};   // last call's level final exponentiations
+    bool rlc_pos_exp = false;         // the TPKE call in progress draws its exponents per group position (pair stage: by set)
     bool lvl_counted = false;         // this call holds a count in the device's in-flight counter (BatchedInflight)
     hipEvent_t rlc_ev[3] = {};
     hipEvent_t rlc_lev_ev[4] = {};    // per level: before sum / Miller / final exp / resolve

@@ -1,6 +1,7 @@
 // lachain_amd/csrc/rlc_common.hpp — device helpers shared by the randomized batch check's kernels (k_batch.hip,
-// k_rlc_rand.hip): batch-exponent key and ChaCha20 scalars, suspect-key bitmap, quad-major SoA records, the joint
-// (a + b lambda) ladders and the validators' fixed-base tables.
+// k_rlc_rand.hip): batch-exponent key and ChaCha20 scalars (per share, or per group position for TPKE), suspect-key
+// bitmap, quad-major SoA records, the joint (a + b lambda) ladders (per lane and wave-uniform) and the validators'
+// fixed-base tables.
 #pragma once
 #include "kcommon.hpp"
 
@@ -32,17 +33,24 @@ DI u32 rotl32(u32 x, int r) { return (x << r) | (x >> (32 - r)); }
     c += d; b ^= c; b = rotl32(b, 12);         \
     a += b; d ^= a; d = rotl32(d, 8);          \
     c += d; b ^= c; b = rotl32(b, 7);
-// share exponent s_i = a_i + b_i lambda (lambda = z^2 - 1, phi(x, y) = (beta x, y)) from the 32-bit words a_i, b_i of
-// ChaCha20 block i: a_i P + b_i phi(P) takes 32 shared doublings.  phi acts as lambda on the r-torsion and the reduced
+// exponent s = a + b lambda (lambda = z^2 - 1, phi(x, y) = (beta x, y)) from the 32-bit words a, b of ChaCha20
+// block (ctr, dom): a P + b phi(P) takes 32 shared doublings.  dom = 0, ctr = i: the per-share exponent s_i (threshold
+// signatures; TPKE with lcb_set_rlc_share_exponents).  dom = RLC_DOM_POS, ctr = bin: the TPKE exponent t[set][pos] of
+// the share at position pos of a level-1 group of set `set` (bin = 32 set + pos, k_batch.hip header); the domain
+// word keeps the two uses on disjoint blocks of the stream.  phi acts as lambda on the r-torsion and the reduced
 // pairing kills every other component of an E(Fp) point, so e(a P + b phi(P), Q) = e(P, Q)^(a + b lambda) for ANY
 // P on the curve; the 2^64 pairs (a, b) give 2^64 distinct exponents mod r (a + b lambda < 2^160 < r), none zero
 // ((0, 0) -> (1, 0)): the soundness of a uniform 64-bit exponent.
-DI void rlc_scalar(const rlc_key &key, u32 i, u32 &a, u32 &b) {
+#define RLC_DOM_POS 1u
+#define RLC_POS_CAP 32u                                // positions per level-1 group (its share cap)
+#define RLC_POS_SETS 4u                                // sets of exponents: a group of ciphertext c uses set c & 3
+#define RLC_POS_BINS (RLC_POS_SETS * RLC_POS_CAP)
+DI void rlc_scalar_dom(const rlc_key &key, u32 ctr, u32 dom, u32 &a, u32 &b) {
     u32 x[16], s[16];
     s[0] = 0x61707865u; s[1] = 0x3320646eu; s[2] = 0x79622d32u; s[3] = 0x6b206574u;
 #pragma unroll
     for (int j = 0; j < 8; j++) s[4 + j] = key.k[j];
-    s[12] = i; s[13] = 0; s[14] = key.nonce[0]; s[15] = key.nonce[1];
+    s[12] = ctr; s[13] = dom; s[14] = key.nonce[0]; s[15] = key.nonce[1];
 #pragma unroll
     for (int j = 0; j < 16; j++) x[j] = s[j];
 #pragma unroll 1
@@ -60,6 +68,7 @@ DI void rlc_scalar(const rlc_key &key, u32 i, u32 &a, u32 &b) {
     b = x[1] + s[1];
     if ((a | b) == 0) a = 1;
 }
+DI void rlc_scalar(const rlc_key &key, u32 i, u32 &a, u32 &b) { rlc_scalar_dom(key, i, 0, a, b); }
 
 // ---------------------------------------------------------------- quad-major SoA records (NW words, NW % 4 == 0)
 template <int NW> DI void soa_store(u32 *base, size_t n, size_t i, const void *v) {
@@ -157,6 +166,17 @@ DI void g1_mul_ab_inl(g1 &r, const g1a &P, u32 a, u32 b) {
         if (da | db) jac_add_aff(r, r, da ? (db ? b2x : P.x) : bx, (da & db) ? ny : P.y);
     }
 #endif
+}
+// The same ladder for a wave whose lanes may all hold one exponent (TPKE position exponents with the lanes sorted by
+// bin: every wave but those that straddle a bin boundary).  When the ballot says every active lane agrees with the
+// first, the exponent is taken from that lane: it is wave-uniform (scalar registers), so a column with a = b = 0 is
+// skipped by a scalar branch and the wave issues the ~24 additions its exponent needs instead of 32.  A mixed wave
+// takes the per-lane ladder; both give the same point.
+DI void g1_mul_ab_wave(g1 &r, const g1a &P, u32 a, u32 b) {
+    if (P.inf) { jac_set_inf(r); return; }       // (leaves the ballot to the lanes that run a ladder)
+    const u32 a0 = (u32)__builtin_amdgcn_readfirstlane((int)a), b0 = (u32)__builtin_amdgcn_readfirstlane((int)b);
+    if (__ballot(a != a0 || b != b0) == 0) g1_mul_ab_inl(r, P, a0, b0);
+    else g1_mul_ab_inl(r, P, a, b);
 }
 // G2 form of g1_mul_ab_inl: a S + b psi^4(S) with the point arithmetic inlined; lean form: x, y and beta x live, the
 // psi^4 addend's beta^2 x = -(x + beta x) and the joint addend psi^2(S) = (beta x, -y) formed per column

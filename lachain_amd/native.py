@@ -63,6 +63,9 @@ _SIGS = {
     "lcb_test_inject_failure": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "lcb_set_lines_coop_max": (ctypes.c_int, [ctypes.c_int]),
     "lcb_set_keys_first": (ctypes.c_int, [ctypes.c_int]),
+    "lcb_set_rlc_share_exponents": (ctypes.c_int, [ctypes.c_int]),
+    "lcb_set_rlc_lane_permutation": (ctypes.c_int, [ctypes.c_int]),
+    "lcb_set_rlc_pos_table_min": (ctypes.c_int, [ctypes.c_uint32]),
     "lcb_test_linesets": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t,
                                           ctypes.c_void_p, ctypes.c_void_p]),
     "lcb_tpke_verify_shares": (ctypes.c_int, [c_u8p, c_size, c_u8p, c_size, c_u8p, c_u8p, c_u8p, c_u32p, c_size,
@@ -1261,6 +1264,21 @@ def set_lines_coop_max(max_sets):
 def set_keys_first(on):
     """fused batched calls: the key tables before the preparation fork (default on)"""
     _tuning(lib().lcb_set_keys_first(1 if on else 0), "set_keys_first")
+
+
+def set_rlc_share_exponents(on):
+    """batched TPKE check: one exponent per share (on) instead of one per group position (default off)"""
+    _tuning(lib().lcb_set_rlc_share_exponents(1 if on else 0), "set_rlc_share_exponents")
+
+
+def set_rlc_lane_permutation(on):
+    """batched TPKE check: the randomisation's lanes sorted by exponent (default on)"""
+    _tuning(lib().lcb_set_rlc_lane_permutation(1 if on else 0), "set_rlc_lane_permutation")
+
+
+def set_rlc_pos_table_min(shares_per_key):
+    """batched TPKE check: the keys' per-position table from this many shares per key (default 512; 0: always)"""
+    _tuning(lib().lcb_set_rlc_pos_table_min(int(shares_per_key)), "set_rlc_pos_table_min")
 
 
 def set_wave_priority(on):
