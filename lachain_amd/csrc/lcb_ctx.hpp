@@ -103,6 +103,84 @@ enum RlcMsStat {      // lcb_ctx::rlc_ms, accumulated over the levels
     RLC_MS_N
 };
 
+
+// The named workspaces below belong to device-path code (what the *_dev forms reach), each grown on demand by the function
+// named last in its line.  What a host-pointer form itself uploads, receives or scratches in has no name: HostCall
+// (host_call.hpp) hands it slots of lcb_ctx::stage[] in request order.
+enum { STAGE_SLOTS = 20 };
+enum CoopBuf {        // lcb_ctx::t_coop, small exact TPKE batches on the cooperative kernels (n: the call's shares)
+    COOP_PTS,         // per share, its two G1 points (U_i, Y_i), 2 n affine records; tpke_verify_core
+    COOP_DESC,        // per share, the check's descriptor, 16 B; the same
+    COOP_FLAGS,       // the cooperative Miller kernel's two flag bytes per share, 2 n B; the same
+    COOP_N
+};
+enum LagBuf {         // lcb_ctx::lag, Lagrange interpolation at 0 (ne: entries over all problems)
+    LAG_LAMBDA,       // the coefficients, ne Fr values; lagrange_enqueue
+    LAG_PARTS,        // lambda_i y_i, ne Jacobian G1 / G2 records; the same
+    LAG_PARTS_OK,     // their validity, ne B; the same
+    LAG_LANES_WS,     // the persistent multiplication grid's workspace (lcbk_lanes_ws_bytes); the same
+    LAG_PREFIX,       // the batch inversion's prefix products, ne Fr values; the same
+    LAG_N
+};
+enum SelBuf {         // lcb_ctx::sel, the first k valid shares of every group (ne = groups x k)
+    SEL_XS,           // their evaluation points, 32 ne B; assemble_enqueue
+    SEL_YS,           // their wire points, 48 / 96 ne B; the same
+    SEL_OFF,          // the problems' entry offsets, groups + 1 words; the same
+    SEL_SRC,          // G2: each entry's share index into s_dec, ne words; the same
+    SEL_N
+};
+enum MsmBuf {         // lcb_ctx::msm, the Pippenger MSM (m = points x windows digit records, nb buckets)
+    MSM_KEYS,         // the records' bucket keys, m words; msm_enqueue
+    MSM_KEYS2,        // the radix sort's second key buffer, m words; the same
+    MSM_VALS,         // the records' point indices, m words; the same
+    MSM_VALS2,        // the sort's second value buffer, m words; the same
+    MSM_START,        // per bucket, its first record, nb words; the same
+    MSM_END,          // per bucket, one past its last record, nb words; the same
+    MSM_BUCKETS,      // the bucket sums, nb Jacobian records; the same
+    MSM_SEGS,         // the bucket reduction's segment sums, n_seg Jacobian records; the same
+    MSM_L1,           // the per-window tree reduction's other buffer, n_l1 Jacobian records; the same
+    MSM_WINS,         // the window sums, one Jacobian record per key window; the same
+    MSM_SORT_TMP,     // the radix sort's temporary storage (lcbk_sort_pairs' query); the same
+    MSM_PHI,          // GLV form: phi(P) of every point, 96 n B; the same
+    MSM_CHUNK_HEAD,   // record-balanced accumulation: each chunk's head partial, one Jacobian record; the same
+    MSM_CHUNK_TAIL,   // and its tail partial; the same
+    MSM_JAC_SUM,      // the sum of the ranks' partial results, one Jacobian record; lcb_ctx_g1_jac_sum_dev
+    MSM_N
+};
+enum EcBuf {          // lcb_ctx::ec, ECDSA verification (n signatures)
+    EC_JOBS,          // the job records, lcbk_secp_job_bytes() n; verify_enqueue
+    EC_HASH,          // the header hashes when the call hashes first, 32 n B; the same
+    EC_HASH_OK,       // their validity, n B; the same
+    EC_N
+};
+enum ErBuf {          // lcb_ctx::er, public-key recovery (n signatures)
+    ER_JOBS,          // the job records, lcbk_secp_rjob_bytes() n; recover_enqueue
+    ER_PTS,           // the Jacobian results, lcbk_secp_rpoint_bytes() n; the same
+    ER_N
+};
+enum EciesBuf {       // lcb_ctx::ecies, the ECIES envelope (n items); the secret-bearing ones are cleared after use
+    ECIES_JOBS,       // the ECDH job records (the scalars' digits), lcbk_ecdh_job_bytes() n; ecdh_core
+    ECIES_PTS,        // the Jacobian results, lcbk_ecdh_point_bytes() n; the same
+    ECIES_KEYS,       // the session keys of the fused envelope calls, 32 n B; envelope_encrypt_dev / envelope_decrypt_dev
+    ECIES_EOK,        // the ECDH validity, n B; the same two
+    ECIES_EPH,        // the ephemeral public keys, 33 n B; envelope_encrypt_dev
+    ECIES_POK,        // their validity, n B; the same
+    ECIES_OFF,        // the plaintext offsets of a decryption, n + 1 u64; gcm_decrypt_dev / envelope_decrypt_dev
+    ECIES_N
+};
+enum TxBuf {          // lcb_ctx::tx, transaction hashing and receipts (n transactions)
+    TX_RAW,           // the raw hashes, 32 n B; receipts_enqueue
+    TX_FLAGS,         // hash-match, then recovered flags, 2 n B; the same
+    TX_ADDR,          // the recovered addresses, 20 n B; the same
+    TX_ROOTS,         // the blocks' roots and their status, 33 B per block; the same
+    TX_LONG,          // the count and list of long items k_tx_hash leaves to k_tx_hash_long, n + 1 words; hash_enqueue
+    TX_N
+};
+enum TrieBuf {        // lcb_ctx::trie, the state trie
+    TRIE_LIST,        // the flat call's count and list of internal nodes, n + 1 words; flat_enqueue
+    TRIE_ROOT_WS,     // the root builder's workspace (lcbk_trie_root_ws_bytes); root_enqueue
+    TRIE_N
+};
 struct lcb_ctx {
     std::recursive_mutex mu;        // one enqueue at a time per context (contexts may be shared by threads)
     int device = 0;
@@ -115,7 +193,7 @@ struct lcb_ctx {
     DevBuf t_lines, t_ctok, t_keys, t_f;
     DevBuf t_ctg2;                    // per ciphertext: W in G2, decided from its line set; written by every TPKE
                                       // preparation (tpke_prepare, the fused batched call), read by the batch check's sums
-    DevBuf t_coop[3];                // small exact batches on the cooperative kernels: point records, checks, flags
+    DevBuf t_coop[COOP_N];           // small exact batches on the cooperative kernels
     // prepared-ciphertext cache of lcb_tpke_verify_shares_cached (line sets + validity per slot, keyed by the bytes)
     DevBuf cc_lines, cc_ok;
     std::unordered_map<std::string, uint32_t> cc_map;
@@ -138,13 +216,19 @@ struct lcb_ctx {
     size_t s_n_msgs = 0, s_n_pks = 0;
     uint64_t s_gen = 0;
     bool s_ready = false;
-    // Lagrange / assembly / MSM / staging
-    DevBuf lag[5], sel[4], msm[15], in[8], out[4], dkg[9];
-    DevBuf lws;                       // lanetab.hpp workspaces of the persistent scalar-multiplication grids
-    DevBuf mcl[10];                   // the mcl surface's pairing / multi-scalar / Horner / Lagrange staging
+    // the host-pointer forms' transient buffers, handed out by HostCall (host_call.hpp) in request order.  The largest
+    // taker at present is lcb_dkg_commitment_eval's exact form with 15 (5 inputs, 2 outputs, 8 of scratch; 14 distinct
+    // buffers before there was a HostCall); next come lcb_tpke_verify_shares_cached (11) and lcb_debug_tpke_miller (10).  The rest is headroom; one request too many
+    // fails the call
+    DevBuf stage[STAGE_SLOTS];
+    int stage_next = 0;               // HostCall's cursor: the first free slot
+    // Lagrange / assembly / MSM
+    DevBuf lag[LAG_N], sel[SEL_N], msm[MSM_N];
+    DevBuf lws;                       // lanetab.hpp workspaces of the persistent scalar-multiplication grids (HostCall::lws)
+    DevBuf merkle_ws;                 // MerkleTree.ComputeRoot's level workspace, 32 B per hash; lcb_ctx_merkle_root_dev
     // mclBn_pairing's cache of G2 line sets (pc_lines: slot k = Q_k's set and the infinity set), least recently used
     // slot replaced: the protocol pairs every share of a ciphertext / coin with the same H, W (TPKE/PublicKey.cs:91).
-    // A buffer of its own: the other mcl calls' staging (mcl[]) must not overwrite cached sets between pairings
+    // A buffer of its own: no other call's staging may overwrite cached sets between pairings
     DevBuf pc_lines;
     std::vector<uint32_t> pc_keys;    // 72 words (the mclBnG2 record) per slot
     std::vector<uint64_t> pc_used;    // last use (0: empty)
@@ -183,33 +267,27 @@ struct lcb_ctx {
     bool fork_ready = false;
     hipEvent_t msm_ev[7] = {};
     bool msm_ev_ready = false, msm_ran = false;
-    // secp256k1 ECDSA (lcb_ecdsa.cpp): job records / header hashes / staging, and the host API's cached key set
-    DevBuf ec[6];
+    // secp256k1 ECDSA (lcb_ecdsa.cpp): job records and header hashes, and the host API's cached key set
+    DevBuf ec[EC_N];
     hipEvent_t ec_ev[4] = {};         // around header hash / scalars / verify of the last verification
     bool ec_ev_ready = false, ec_ran = false, ec_hashed = false;
     struct lcb_ecdsa_keyset *ec_cache = nullptr;
     std::vector<uint8_t> ec_cache_keys;
     size_t ec_cache_pk_len = 0;
-    // public-key recovery (lcb_ecdsa.cpp): job records, Jacobian results, staging of the host-pointer forms
-    DevBuf er[6];
+    // public-key recovery (lcb_ecdsa.cpp): job records and Jacobian results
+    DevBuf er[ER_N];
     hipEvent_t er_ev[4] = {};         // around scalars / recovery / finish of the last recovery
     bool er_ev_ready = false, er_ran = false;
-    // reliable-broadcast Merkle layer and block roots (lcb_rbc.cpp): staging, offsets, RS positions / matrices, trees
-    DevBuf rbc[12];
-    // secp256k1 ECIES (lcb_ecies.cpp): [0] job records, [1] Jacobian results, [2] session keys, [3] ECDH validity,
-    // [4] ephemeral public keys, [5] their validity, [6] plaintext offsets, [7..13] staging of the host-pointer forms
-    DevBuf ecies[14];
+    // secp256k1 ECIES (lcb_ecies.cpp)
+    DevBuf ecies[ECIES_N];
     hipEvent_t ecies_ev[5] = {};      // around scalars / multiplication / finish / GCM of the last call
     bool ecies_ev_ready = false, ecies_ran = false;
-    // transaction hashing and receipt verification (lcb_txhash.cpp): [0] raw hashes, [1] hash-match / recovered flags,
-    // [2] recovered addresses, [3] block roots and their status, [4..11] staging of the host-pointer forms, [12] the
-    // count and list of long items that k_tx_hash leaves to k_tx_hash_long
-    DevBuf tx[13];
+    // transaction hashing and receipt verification (lcb_txhash.cpp)
+    DevBuf tx[TX_N];
     hipEvent_t tx_ev[4] = {};         // around hashing / recovery and decision / roots of the last call
     bool tx_ev_ready = false, tx_ran = false;
-    // state trie (lcb_trie.cpp): [0] the flat call's list of internal nodes, [1] the root builder's workspace,
-    // [2..11] staging of the host-pointer forms
-    DevBuf trie[12];
+    // state trie (lcb_trie.cpp)
+    DevBuf trie[TRIE_N];
 };
 
 // Enqueue scope: exclusive use of the context, stream ordered after the context's previous work, and the

@@ -125,7 +125,7 @@ int verify_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *accept, const uint8_t *ha
     if (sig_len == 0 || sig_len > 4096) { set_err("ecdsa: bad signature stride"); return -1; }
     const void *gt = gen_table(s);
     if (!gt) return -1;
-    void *jobs = c->ec[0].get(lcbk_secp_job_bytes() * n);
+    void *jobs = c->ec[EC_JOBS].get(lcbk_secp_job_bytes() * n);
     if (!jobs) { set_err("device allocation failed"); return -1; }
     if (!c->ec_ev_ready) {
         for (auto &e : c->ec_ev)
@@ -136,7 +136,7 @@ int verify_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *accept, const uint8_t *ha
     (void)hipEventRecord(c->ec_ev[0], s);
     c->ec_hashed = hashes == nullptr;
     if (!hashes) {
-        uint8_t *h = (uint8_t *)c->ec[1].get(32 * n), *po = (uint8_t *)c->ec[2].get(n);
+        uint8_t *h = (uint8_t *)c->ec[EC_HASH].get(32 * n), *po = (uint8_t *)c->ec[EC_HASH_OK].get(n);
         if (!h || !po) { set_err("device allocation failed"); return -1; }
         lcbk_secp_header_hash(s, headers, (u32)n, era, h, po);
         hashes = h;
@@ -179,21 +179,16 @@ int verify_host(uint8_t *accept, const uint8_t *hashes, const uint8_t *headers, 
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     const lcb_ecdsa_keyset *ks = cached_keyset(c, pubkeys, pk_len, n_keys);
     if (!ks) return -1;
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    size_t in_bytes = headers ? 112 * n : 32 * n;
-    uint8_t *din = (uint8_t *)c->ec[3].get(in_bytes), *dsig = (uint8_t *)c->ec[4].get(sig_len * n);
-    int32_t *didx = (int32_t *)c->ec[5].get(4 * n);
-    uint8_t *dout = (uint8_t *)c->out[0].get(n);
-    if (!din || !dsig || !didx || !dout) { set_err("device allocation failed"); return -1; }
-    hipMemcpyAsync(din, headers ? headers : hashes, in_bytes, hipMemcpyHostToDevice, s);
-    hipMemcpyAsync(dsig, sigs, sig_len * n, hipMemcpyHostToDevice, s);
-    hipMemcpyAsync(didx, key_idx, 4 * n, hipMemcpyHostToDevice, s);
-    if (verify_enqueue(c, s, dout, headers ? nullptr : din, headers ? din : nullptr, era, dsig, sig_len, didx, n, ks,
+    HostCall h(c, "ecdsa verify");
+    const uint8_t *din = h.in(headers ? headers : hashes, headers ? 112 * n : 32 * n), *dsig = h.in(sigs, sig_len * n);
+    const int32_t *didx = h.in(key_idx, n);
+    uint8_t *dout = h.out<uint8_t>(n);
+    if (!h.ok()) return -1;
+    if (verify_enqueue(c, h.s, dout, headers ? nullptr : din, headers ? din : nullptr, era, dsig, sig_len, didx, n, ks,
                        use_new_chain_id, chain_id))
         return -1;
-    hipMemcpyAsync(accept, dout, n, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "ecdsa verify") ? 0 : -1;
+    h.back(accept, dout, n);
+    return h.finish();
 }
 
 }  // namespace
@@ -291,15 +286,14 @@ extern "C" int lcb_header_keccak_batch(uint8_t *hashes, const lcb_block_header *
     lcb_ctx *c = ctx_sync();
     if (!c) return -1;
     if (!n) return 0;
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    uint8_t *dh = (uint8_t *)c->ec[3].get(112 * n), *dout = (uint8_t *)c->ec[1].get(32 * n), *po = (uint8_t *)c->ec[2].get(n);
-    if (!dh || !dout || !po) { set_err("device allocation failed"); return -1; }
-    hipMemcpyAsync(dh, headers, 112 * n, hipMemcpyHostToDevice, s);
-    lcbk_secp_header_hash(s, dh, (u32)n, 0, dout, po);
+    HostCall h(c, "header hash");
+    const uint8_t *dh = h.in((const uint8_t *)headers, 112 * n);
+    uint8_t *dout = h.out<uint8_t>(32 * n), *po = h.out<uint8_t>(n);
+    if (!h.ok()) return -1;
+    lcbk_secp_header_hash(h.s, dh, (u32)n, 0, dout, po);
     if (!launch_ok("header hash launch")) return -1;
-    hipMemcpyAsync(hashes, dout, 32 * n, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "header hash") ? 0 : -1;
+    h.back(hashes, dout, 32 * n);
+    return h.finish();
 }
 
 // ------------------------------------------------------------------ signing side (key derivation, SignHashed with given
@@ -341,33 +335,29 @@ extern "C" int lcb_ecdsa_pubkey_batch(uint8_t *out33, uint8_t *ok, const uint8_t
     lcb_ctx *c = ctx_sync();
     if (!c) return -1;
     if (!n) return 0;
-    Enq q(c, c->stream);
-    uint8_t *dp = (uint8_t *)c->ec[3].get(32 * n), *dout = (uint8_t *)c->ec[4].get(34 * n);
-    if (!dp || !dout) { set_err("device allocation failed"); return -1; }
-    hipMemcpyAsync(dp, privs, 32 * n, hipMemcpyHostToDevice, c->stream);
-    if (lcb_ctx_ecdsa_pubkey_dev(c, dout, dout + 33 * n, dp, n, c->stream)) return -1;
-    hipMemcpyAsync(out33, dout, 33 * n, hipMemcpyDeviceToHost, c->stream);
-    hipMemcpyAsync(ok, dout + 33 * n, n, hipMemcpyDeviceToHost, c->stream);
-    return sync_check(c, "ecdsa pubkey") ? 0 : -1;
+    HostCall h(c, "ecdsa pubkey");
+    const uint8_t *dp = h.in(privs, 32 * n);
+    uint8_t *dout = h.out<uint8_t>(34 * n);
+    if (!h.ok()) return -1;
+    if (lcb_ctx_ecdsa_pubkey_dev(c, dout, dout + 33 * n, dp, n, h.s)) return -1;
+    h.back(out33, dout, 33 * n);
+    h.back(ok, dout + 33 * n, n);
+    return h.finish();
 }
 extern "C" int lcb_ecdsa_sign_hashed_batch(uint8_t *sigs_out, uint8_t *ok, const uint8_t *hashes, const uint8_t *privs,
                                            const uint8_t *nonces, size_t n, int use_new_chain_id, int32_t chain_id) {
     lcb_ctx *c = ctx_sync();
     if (!c) return -1;
     if (!n) return 0;
-    Enq q(c, c->stream);
+    HostCall h(c, "ecdsa sign");
     size_t L = use_new_chain_id ? 66 : 65;
-    uint8_t *din = (uint8_t *)c->ec[3].get(96 * n), *dout = (uint8_t *)c->ec[4].get((L + 1) * n);
-    if (!din || !dout) { set_err("device allocation failed"); return -1; }
-    hipMemcpyAsync(din, hashes, 32 * n, hipMemcpyHostToDevice, c->stream);
-    hipMemcpyAsync(din + 32 * n, privs, 32 * n, hipMemcpyHostToDevice, c->stream);
-    hipMemcpyAsync(din + 64 * n, nonces, 32 * n, hipMemcpyHostToDevice, c->stream);
-    if (lcb_ctx_ecdsa_sign_hashed_dev(c, dout, dout + L * n, din, din + 32 * n, din + 64 * n, n, use_new_chain_id,
-                                      chain_id, c->stream))
-        return -1;
-    hipMemcpyAsync(sigs_out, dout, L * n, hipMemcpyDeviceToHost, c->stream);
-    hipMemcpyAsync(ok, dout + L * n, n, hipMemcpyDeviceToHost, c->stream);
-    return sync_check(c, "ecdsa sign") ? 0 : -1;
+    const uint8_t *dh = h.in(hashes, 32 * n), *dp = h.in(privs, 32 * n), *dk = h.in(nonces, 32 * n);
+    uint8_t *dout = h.out<uint8_t>((L + 1) * n);
+    if (!h.ok()) return -1;
+    if (lcb_ctx_ecdsa_sign_hashed_dev(c, dout, dout + L * n, dh, dp, dk, n, use_new_chain_id, chain_id, h.s)) return -1;
+    h.back(sigs_out, dout, L * n);
+    h.back(ok, dout + L * n, n);
+    return h.finish();
 }
 
 // ------------------------------------------------------------------ public-key recovery (transaction senders)
@@ -402,7 +392,7 @@ int recover_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *pub33, uint8_t *addr20, 
     }
     const void *gt = gen_table(s);
     if (!gt) return -1;
-    void *jobs = c->er[0].get(lcbk_secp_rjob_bytes() * n), *pts = c->er[1].get(lcbk_secp_rpoint_bytes() * n);
+    void *jobs = c->er[ER_JOBS].get(lcbk_secp_rjob_bytes() * n), *pts = c->er[ER_PTS].get(lcbk_secp_rpoint_bytes() * n);
     if (!jobs || !pts) { set_err("device allocation failed"); return -1; }
     (void)hipEventRecord(c->er_ev[0], s);
     lcbk_secp_rec_scalars(s, hashes, sigs, (u32)sig_len, want, chain_id, special, (u32)n, jobs);
@@ -422,25 +412,20 @@ int recover_host(uint8_t *pub33, uint8_t *addr20, uint8_t *ok, uint8_t *accept, 
     if (!c) return -1;
     if (!n) return 0;
     if (sig_len == 0 || sig_len > 4096) { set_err("ecdsa recover: bad signature stride"); return -1; }
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    uint8_t *dh = (uint8_t *)c->er[2].get(32 * n), *dsig = (uint8_t *)c->er[3].get(sig_len * n);
-    uint8_t *dfrom = from20 ? (uint8_t *)c->er[4].get(20 * n) : nullptr;
-    uint8_t *dout = (uint8_t *)c->er[5].get(55 * n);        // 33 key | 20 address | ok | accept
-    if (!dh || !dsig || (from20 && !dfrom) || !dout) { set_err("device allocation failed"); return -1; }
+    HostCall h(c, "ecdsa recover");
+    const uint8_t *dh = h.in(hashes, 32 * n), *dsig = h.in(sigs, sig_len * n);
+    const uint8_t *dfrom = from20 ? h.in(from20, 20 * n) : nullptr;
+    uint8_t *dout = h.out<uint8_t>(55 * n);        // 33 key | 20 address | ok | accept
+    if (!h.ok()) return -1;
     uint8_t *dpub = dout, *daddr = dout + 33 * n, *dok = dout + 53 * n, *dacc = dout + 54 * n;
-    hipMemcpyAsync(dh, hashes, 32 * n, hipMemcpyHostToDevice, s);
-    hipMemcpyAsync(dsig, sigs, sig_len * n, hipMemcpyHostToDevice, s);
-    if (from20) hipMemcpyAsync(dfrom, from20, 20 * n, hipMemcpyHostToDevice, s);
-    if (recover_enqueue(c, s, pub33 ? dpub : nullptr, addr20 ? daddr : nullptr, ok ? dok : nullptr,
+    if (recover_enqueue(c, h.s, pub33 ? dpub : nullptr, addr20 ? daddr : nullptr, ok ? dok : nullptr,
                         accept ? dacc : nullptr, dh, dsig, sig_len, dfrom, n, special, use_new_chain_id, chain_id))
         return -1;
-    if (pub33) hipMemcpyAsync(pub33, dpub, 33 * n, hipMemcpyDeviceToHost, s);
-    if (addr20) hipMemcpyAsync(addr20, daddr, 20 * n, hipMemcpyDeviceToHost, s);
-    if (ok) hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, s);
-    if (accept) hipMemcpyAsync(accept, dacc, n, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "ecdsa recover") ? 0 : -1;
+    h.back(pub33, dpub, 33 * n);
+    h.back(addr20, daddr, 20 * n);
+    h.back(ok, dok, n);
+    h.back(accept, dacc, n);
+    return h.finish();
 }
 }  // namespace
 
@@ -537,21 +522,16 @@ extern "C" int lcb_keccak256_batch(uint8_t *out32, const uint8_t *data, const ui
     lcb_ctx *c = ctx_sync();
     if (!c) return -1;
     if (!n) return 0;
-    for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) { set_err("keccak256: offsets must not decrease"); return -1; }
-    size_t bytes = (size_t)(off[n] - off[0]);
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    uint8_t *dd = (uint8_t *)c->er[2].get(bytes), *dout = (uint8_t *)c->er[5].get(32 * n);
-    uint64_t *doff = (uint64_t *)c->er[3].get(8 * (n + 1));
-    if (!dd || !dout || !doff) { set_err("device allocation failed"); return -1; }
-    if (bytes) hipMemcpyAsync(dd, data + off[0], bytes, hipMemcpyHostToDevice, s);
-    hipMemcpyAsync(doff, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, s);
-    if (lcb_ctx_keccak256_dev(c, dout, dd, doff, n, s)) return -1;
-    hipMemcpyAsync(out32, dout, 32 * n, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "keccak256") ? 0 : -1;
+    std::vector<uint64_t> rel;
+    if (!rebase(rel, off, n, "keccak256: offsets must not decrease")) return -1;
+    HostCall h(c, "keccak256");
+    const uint8_t *dd = h.in(data + off[0], (size_t)rel[n]);
+    const uint64_t *doff = h.in(rel.data(), n + 1);
+    uint8_t *dout = h.out<uint8_t>(32 * n);
+    if (!h.ok()) return -1;
+    if (lcb_ctx_keccak256_dev(c, dout, dd, doff, n, h.s)) return -1;
+    h.back(out32, dout, 32 * n);
+    return h.finish();
 }
 
 // ------------------------------------------------------------------ test hook
@@ -565,15 +545,12 @@ extern "C" int lcb_debug_secp_op(int op, const uint32_t *a, const uint32_t *b, s
     const bool binary = op == 0 || op == 2 || op == 3 || op == 9 || op == 10 || op == 15 || op == 16;
     if (!a || !out || (binary && !b)) { set_err("debug secp op: missing operand"); return -1; }
     const size_t in_w = lcbk_secp_debug_in_words() * n, out_w = lcbk_secp_debug_out_words() * n;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    u32 *da = (u32 *)c->er[2].get(4 * in_w), *db = (u32 *)c->er[3].get(4 * in_w), *dout = (u32 *)c->er[5].get(4 * out_w);
-    if (!da || !db || !dout) { set_err("device allocation failed"); return -1; }
-    hipMemcpyAsync(da, a, 4 * in_w, hipMemcpyHostToDevice, s);
-    if (b) hipMemcpyAsync(db, b, 4 * in_w, hipMemcpyHostToDevice, s);
-    lcbk_secp_debug(s, op, da, b ? db : da, (u32)n, dout);
+    HostCall h(c, "debug secp op");
+    const u32 *da = h.in(a, in_w), *db = b ? h.in(b, in_w) : da;
+    u32 *dout = h.out<u32>(out_w);
+    if (!h.ok()) return -1;
+    lcbk_secp_debug(h.s, op, da, db, (u32)n, dout);
     if (!launch_ok("debug secp op launch")) return -1;
-    hipMemcpyAsync(out, dout, 4 * out_w, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "debug secp op") ? 0 : -1;
+    h.back(out, dout, 4 * out_w);
+    return h.finish();
 }

@@ -365,11 +365,8 @@ void ctx_free(lcb_ctx *c) {
     c->lws.release();
     for (auto &b : c->sel) b.release();
     for (auto &b : c->msm) b.release();
-    for (auto &b : c->in) b.release();
-    for (auto &b : c->out) b.release();
-    for (auto &b : c->dkg) b.release();
-    for (auto &b : c->mcl) b.release();
-    for (auto &b : c->rbc) b.release();
+    for (auto &b : c->stage) b.release();
+    c->merkle_ws.release();
     c->pc_lines.release();
     for (auto &b : c->t_coop) b.release();
     c->cc_lines.release();
@@ -530,9 +527,9 @@ int tpke_verify_core(lcb_ctx *c, const u32 *lines, const uint8_t *ctok, size_t n
         // (k_coop.hip) instead of one, below the size where the one-lane kernels fill the GPU
         // (never above one chunk: the cooperative buffers below are sized for n)
         const bool coop = n <= g_coop_max.load() && n <= LCB_VERIFY_CHUNK;
-        void *gpts = coop ? c->t_coop[0].get(n * 2 * LCB_G1A_ST_BYTES) : nullptr;
-        void *desc = coop ? c->t_coop[1].get(n * 16) : nullptr;
-        uint8_t *fl = coop ? (uint8_t *)c->t_coop[2].get(2 * n) : nullptr;
+        void *gpts = coop ? c->t_coop[COOP_PTS].get(n * 2 * LCB_G1A_ST_BYTES) : nullptr;
+        void *desc = coop ? c->t_coop[COOP_DESC].get(n * 16) : nullptr;
+        uint8_t *fl = coop ? (uint8_t *)c->t_coop[COOP_FLAGS].get(2 * n) : nullptr;
         if (coop && (!gpts || !desc || !fl)) { set_err("device allocation failed"); return -1; }
         for (size_t o = 0; o < n; o += LCB_VERIFY_CHUNK) {
             const size_t m = n - o < LCB_VERIFY_CHUNK ? n - o : LCB_VERIFY_CHUNK;
@@ -619,15 +616,15 @@ int ts_verify_prepared(lcb_ctx *c, uint8_t *d_accept, size_t n, size_t n_pks, si
 int lcb_int::lagrange_enqueue(lcb_ctx *c, int g, uint8_t *dout, uint8_t *dst, const uint8_t *dx, const uint8_t *dy,
                               const uint32_t *doff, size_t np, size_t ne, hipStream_t s, const u32 *src, bool pairs) {
     if (np > 0xffffffffu || ne > 0xffffffffu) { set_err("lagrange: batch too large"); return -1; }
-    void *lam = c->lag[0].get(LCB_FR_BYTES * (ne ? ne : 1));
-    void *pre = c->lag[4].get(LCB_FR_BYTES * (ne ? ne : 1));      // the batch inversion's prefix products
-    void *parts = c->lag[1].get((g == 1 ? LCB_G1_JAC_BYTES : LCB_G2_JAC_BYTES) * (ne ? ne : 1));
-    uint8_t *pok = (uint8_t *)c->lag[2].get(ne ? ne : 1);
+    void *lam = c->lag[LAG_LAMBDA].get(LCB_FR_BYTES * (ne ? ne : 1));
+    void *pre = c->lag[LAG_PREFIX].get(LCB_FR_BYTES * (ne ? ne : 1));      // the batch inversion's prefix products
+    void *parts = c->lag[LAG_PARTS].get((g == 1 ? LCB_G1_JAC_BYTES : LCB_G2_JAC_BYTES) * (ne ? ne : 1));
+    uint8_t *pok = (uint8_t *)c->lag[LAG_PARTS_OK].get(ne ? ne : 1);
     if (!lam || !pre || !parts || !pok) { set_err("device allocation failed"); return -1; }
     lcbk_lagrange_coeffs(dim3(nblk(np)), s, dx, doff, (u32)np, lam, pre, dst);
     if (ne) {
         const int which = g == 1 ? 1 : pairs ? 3 : 2;   // pairs: even problem offsets (assembly with even k)
-        u32 *ws = (u32 *)c->lag[3].get(lcbk_lanes_ws_bytes(which, (u32)ne));
+        u32 *ws = (u32 *)c->lag[LAG_LANES_WS].get(lcbk_lanes_ws_bytes(which, (u32)ne));
         if (!ws) { set_err("device allocation failed (Lagrange lanes workspace)"); return -1; }
         if (g == 1) lcbk_g1_mul_lanes(s, dy, lam, (u32)ne, parts, pok, ws);
         else if (pairs)   // two entries per lane, shared doublings
@@ -647,10 +644,10 @@ int assemble_enqueue(lcb_ctx *c, int g, uint8_t *out, uint8_t *status, const uin
     if (k == 0 || k > per_group) { set_err("assemble: need 0 < k <= shares per group"); return -1; }
     size_t pb = g == 1 ? 48 : 96, ne = n_groups * k;
     if (ne > 0xffffffffu || (size_t)n_groups * per_group > 0xffffffffu) { set_err("assemble: batch too large"); return -1; }
-    uint8_t *xs = (uint8_t *)c->sel[0].get(32 * ne), *ys = (uint8_t *)c->sel[1].get(pb * ne);
-    u32 *off = (u32 *)c->sel[2].get(4 * (n_groups + 1));
+    uint8_t *xs = (uint8_t *)c->sel[SEL_XS].get(32 * ne), *ys = (uint8_t *)c->sel[SEL_YS].get(pb * ne);
+    u32 *off = (u32 *)c->sel[SEL_OFF].get(4 * (n_groups + 1));
     // G2 (signature shares): each entry's share index, so the lanes can reuse the batched check's decoded shares
-    u32 *src = g == 2 && c->s_dec_n ? (u32 *)c->sel[3].get(4 * ne) : nullptr;
+    u32 *src = g == 2 && c->s_dec_n ? (u32 *)c->sel[SEL_SRC].get(4 * ne) : nullptr;
     if (!xs || !ys || !off) { set_err("device allocation failed"); return -1; }
     lcbk_select_first_valid(dim3(nblk(n_groups)), s, accept, pts, (u32)pb, (u32)per_group, (u32)k, (u32)n_groups, xs,
                             ys, off, order, src);
@@ -713,21 +710,21 @@ int msm_enqueue(lcb_ctx *cx, void *out_jac, const void *pts, const uint8_t *scal
         cx->msm_ev_ready = true;
     }
     DevBuf *b = cx->msm;
-    u32 *keys = (u32 *)b[0].get(m * 4), *keys2 = (u32 *)b[1].get(m * 4);
-    u32 *vals = (u32 *)b[2].get(m * 4), *vals2 = (u32 *)b[3].get(m * 4);
-    u32 *st = (u32 *)b[4].get((size_t)nb * 4), *en = (u32 *)b[5].get((size_t)nb * 4);
-    void *buckets = b[6].get((size_t)nb * LCB_G1_JAC_BYTES);
-    void *segs = b[7].get((size_t)n_seg * LCB_G1_JAC_BYTES);
-    void *l1 = b[8].get((size_t)n_l1 * LCB_G1_JAC_BYTES);
-    void *wins = b[9].get((size_t)kwin * LCB_G1_JAC_BYTES);
+    u32 *keys = (u32 *)b[MSM_KEYS].get(m * 4), *keys2 = (u32 *)b[MSM_KEYS2].get(m * 4);
+    u32 *vals = (u32 *)b[MSM_VALS].get(m * 4), *vals2 = (u32 *)b[MSM_VALS2].get(m * 4);
+    u32 *st = (u32 *)b[MSM_START].get((size_t)nb * 4), *en = (u32 *)b[MSM_END].get((size_t)nb * 4);
+    void *buckets = b[MSM_BUCKETS].get((size_t)nb * LCB_G1_JAC_BYTES);
+    void *segs = b[MSM_SEGS].get((size_t)n_seg * LCB_G1_JAC_BYTES);
+    void *l1 = b[MSM_L1].get((size_t)n_l1 * LCB_G1_JAC_BYTES);
+    void *wins = b[MSM_WINS].get((size_t)kwin * LCB_G1_JAC_BYTES);
     size_t tb = 0;
     if (n && lcbk_sort_pairs(nullptr, &tb, keys, keys2, vals, vals2, (u32)m, end_bit, s) < 0) { set_err("msm: sort query"); return -1; }
-    void *temp = b[10].get(tb);
+    void *temp = b[MSM_SORT_TMP].get(tb);
     if (!keys || !keys2 || !vals || !vals2 || !st || !en || !buckets || !segs || !l1 || !wins || !temp) {
         set_err("msm: device allocation failed");
         return -1;
     }
-    void *phi = glv ? b[11].get(n * 96) : nullptr;
+    void *phi = glv ? b[MSM_PHI].get(n * 96) : nullptr;
     if (glv && !phi) { set_err("msm: device allocation failed"); return -1; }
     hipEventRecord(cx->msm_ev[0], s);
     if (n && glv) {
@@ -748,7 +745,7 @@ int msm_enqueue(lcb_ctx *cx, void *out_jac, const void *pts, const uint8_t *scal
     if (g_msm_chunk > 0) {                       // record-balanced accumulation (k_msm_chunk_acc)
         const u32 K = (u32)g_msm_chunk.load();
         const size_t nch = (m + K - 1) / K;
-        void *hp = b[12].get((nch ? nch : 1) * LCB_G1_JAC_BYTES), *tp = b[13].get((nch ? nch : 1) * LCB_G1_JAC_BYTES);
+        void *hp = b[MSM_CHUNK_HEAD].get((nch ? nch : 1) * LCB_G1_JAC_BYTES), *tp = b[MSM_CHUNK_TAIL].get((nch ? nch : 1) * LCB_G1_JAC_BYTES);
         if (!hp || !tp) { set_err("msm: device allocation failed"); return -1; }
         if (m) lcbk_msm_chunk_acc(s, pts, phi, (u32)n, keys, vals, (u32)m, K, sentinel, st, en, buckets, hp, tp, L, n_seg);
         lcbk_msm_bucket_fix(s, st, en, K, hp, tp, nb, buckets, L, n_seg);
@@ -887,12 +884,12 @@ extern "C" int lcb_test_linesets(int coop, const uint8_t *g2_wire, const uint8_t
     if (!env_on("LCB_ALLOW_TEST_HOOKS")) { set_err("lcb_test_linesets: needs LCB_ALLOW_TEST_HOOKS=1"); return -1; }
     if (!n || n > 4096) { set_err("lcb_test_linesets: 1..4096 points"); return -1; }
     SYNC_CTX_OR(c, -1)
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
+    HostCall h(c, "lcb_test_linesets");
+    hipStream_t s = h.s;
     const size_t W = LCB_LINESET_BYTES / 4;
-    u32 *lines = (u32 *)c->in[0].get(n * LCB_LINESET_BYTES);
-    uint8_t *dg = (uint8_t *)c->in[1].get(n / 2 + 1);
-    if (!lines || !dg) { set_err("device allocation failed"); return -1; }
+    u32 *lines = h.out<u32>(n * W);
+    uint8_t *dg = h.out<uint8_t>(n / 2 + 1);
+    if (!h.ok()) return -1;
     std::vector<u32> host(n * W, 0u);
     for (size_t k = 0; k < n; k++) {
         fph::g2a a;
@@ -910,14 +907,13 @@ extern "C" int lcb_test_linesets(int coop, const uint8_t *g2_wire, const uint8_t
     if (coop == 2) lcbk_lineset_coop_2w(s, lines, (u32)n, nullptr, dg);     // the fused census's instance (k_prep.hip)
     else if (coop) lcbk_lineset_coop(s, lines, (u32)n, nullptr, dg);
     else lcbk_lineset_fill(dim3(nblk(n)), s, lines, (u32)n, nullptr, dg);
-    hipMemcpyAsync(out, lines, n * LCB_LINESET_BYTES, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(w_g2, dg, n / 2, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "lcb_test_linesets") ? 0 : -1;
+    h.back(out, lines, n * LCB_LINESET_BYTES);
+    h.back(w_g2, dg, n / 2);
+    return h.finish();
 }
 // one cooperative Fp12 operation (k_coop_debug) on n values a (and b) vs the one-lane field.hpp routine: AoS in / out
 extern "C" int lcb_debug_coop_op(int op, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out, uint32_t *ref) {
     SYNC_CTX_OR(c, -1)
-    Enq q(c, c->stream);
     if (!n || n > 65536) { set_err("debug coop op: 1..65536 values"); return -1; }
     const size_t W = (size_t)144 * n;
     std::vector<u32> sa(W * 6, 0), sb(W), so(W), sr(W);
@@ -926,15 +922,15 @@ extern "C" int lcb_debug_coop_op(int op, const uint32_t *a, const uint32_t *b, s
             sa[((size_t)(w >> 2) * n + i) * 4 + (w & 3)] = a[144 * i + w];
             sb[((size_t)(w >> 2) * n + i) * 4 + (w & 3)] = b[144 * i + w];
         }
-    u32 *da = (u32 *)c->out[0].get(W * 24), *db = (u32 *)c->out[1].get(W * 4), *dout = (u32 *)c->out[2].get(W * 4),
-        *dref = (u32 *)c->out[3].get(W * 4);
-    if (!da || !db || !dout || !dref) { set_err("device allocation failed"); return -1; }
-    hipMemcpyAsync(da, sa.data(), W * 24, hipMemcpyHostToDevice, q.s);
-    hipMemcpyAsync(db, sb.data(), W * 4, hipMemcpyHostToDevice, q.s);
-    lcbk_coop_debug(q.s, op, da, db, (u32)n, dout, dref);
-    hipMemcpyAsync(so.data(), dout, W * 4, hipMemcpyDeviceToHost, q.s);
-    hipMemcpyAsync(sr.data(), dref, W * 4, hipMemcpyDeviceToHost, q.s);
-    if (!sync_check(c, "debug coop op")) return -1;
+    HostCall h(c, "debug coop op");
+    u32 *da = h.work(sa.data(), W * 6);
+    const u32 *db = h.in(sb.data(), W);
+    u32 *dout = h.out<u32>(W), *dref = h.out<u32>(W);
+    if (!h.ok()) return -1;
+    lcbk_coop_debug(h.s, op, da, db, (u32)n, dout, dref);
+    h.back(so.data(), dout, W * 4);
+    h.back(sr.data(), dref, W * 4);
+    if (h.finish()) return -1;
     for (size_t i = 0; i < n; i++)
         for (int w = 0; w < 144; w++) {
             out[144 * i + w] = so[((size_t)(w >> 2) * n + i) * 4 + (w & 3)];
@@ -946,20 +942,19 @@ extern "C" int lcb_debug_coop_op(int op, const uint32_t *a, const uint32_t *b, s
 // the nine-lane kernel (coop = 1): tests compare the two bit for bit
 extern "C" int lcb_debug_final_exp(const uint32_t *in, size_t n, uint32_t *out, int coop) {
     SYNC_CTX_OR(c, -1)
-    Enq q(c, c->stream);
     if (!n || n > 65536) { set_err("debug final exp: 1..65536 values"); return -1; }
     std::vector<u32> soa((size_t)144 * n * lcbk_fe_slots(), 0);
     for (size_t i = 0; i < n; i++)
         for (int w = 0; w < 144; w++) soa[((size_t)(w >> 2) * n + i) * 4 + (w & 3)] = in[144 * i + w];
-    u32 *d = (u32 *)c->out[0].get(soa.size() * 4);
-    uint8_t *acc = (uint8_t *)c->out[1].get(n);
-    if (!d || !acc) { set_err("device allocation failed"); return -1; }
-    hipMemcpyAsync(d, soa.data(), soa.size() * 4, hipMemcpyHostToDevice, q.s);
-    hipMemsetAsync(acc, 1, n, q.s);
-    if (coop) lcbk_coop_final_exp_check(q.s, d, (u32)n, acc);
-    else lcbk_final_exp_check(dim3(nblk(n)), q.s, d, (u32)n, acc);
-    hipMemcpyAsync(soa.data(), d, (size_t)144 * n * 4, hipMemcpyDeviceToHost, q.s);
-    if (!sync_check(c, "debug final exp")) return -1;
+    HostCall h(c, "debug final exp");
+    u32 *d = h.work(soa.data(), soa.size());
+    uint8_t *acc = h.out<uint8_t>(n);
+    if (!h.ok()) return -1;
+    hipMemsetAsync(acc, 1, n, h.s);
+    if (coop) lcbk_coop_final_exp_check(h.s, d, (u32)n, acc);
+    else lcbk_final_exp_check(dim3(nblk(n)), h.s, d, (u32)n, acc);
+    h.back(soa.data(), d, (size_t)144 * n * 4);
+    if (h.finish()) return -1;
     for (size_t i = 0; i < n; i++)
         for (int w = 0; w < 144; w++) out[144 * i + w] = soa[((size_t)(w >> 2) * n + i) * 4 + (w & 3)];
     return 0;
@@ -969,7 +964,6 @@ extern "C" int lcb_debug_final_exp(const uint32_t *in, size_t n, uint32_t *out, 
 // squarings in one call (lcb_r_cyc_sqr_n), 4 a^z (lcb_r_pow_z); b is read by ops 0 and 1 only
 extern "C" int lcb_debug_asm_tower(int op, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out) {
     SYNC_CTX_OR(c, -1)
-    Enq q(c, c->stream);
     const int what = op & 255, count = op >> 8;
     if (!n || n > 65536) { set_err("debug asm tower: 1..65536 values"); return -1; }
     if (op < 0 || what > 4 || (what == 3 ? count < 1 || count > 255 : count != 0)) {
@@ -984,12 +978,12 @@ extern "C" int lcb_debug_asm_tower(int op, const uint32_t *a, const uint32_t *b,
             soa[((size_t)(w >> 2) * n + i) * 4 + (w & 3)] = a[144 * i + w];
             if (what < 2) soa[W + ((size_t)(w >> 2) * n + i) * 4 + (w & 3)] = b[144 * i + w];
         }
-    u32 *d = (u32 *)c->out[0].get(soa.size() * 4);
-    if (!d) { set_err("device allocation failed"); return -1; }
-    hipMemcpyAsync(d, soa.data(), soa.size() * 4, hipMemcpyHostToDevice, q.s);
-    lcbk_asm_tower_debug(dim3(nblk(n)), q.s, what, d, (u32)n, (u32)(count ? count : 1));
-    hipMemcpyAsync(soa.data(), d + 2 * W, W * 4, hipMemcpyDeviceToHost, q.s);
-    if (!sync_check(c, "debug asm tower")) return -1;
+    HostCall h(c, "debug asm tower");
+    u32 *d = h.work(soa.data(), soa.size());
+    if (!h.ok()) return -1;
+    lcbk_asm_tower_debug(dim3(nblk(n)), h.s, what, d, (u32)n, (u32)(count ? count : 1));
+    h.back(soa.data(), d + 2 * W, W * 4);
+    if (h.finish()) return -1;
     for (size_t i = 0; i < n; i++)
         for (int w = 0; w < 144; w++) out[144 * i + w] = soa[((size_t)(w >> 2) * n + i) * 4 + (w & 3)];
     return 0;
@@ -1005,26 +999,26 @@ extern "C" int lcb_debug_tpke_miller(uint32_t *f_out, uint8_t *ok_out, size_t n,
     if (!n || n > 65536 || !n_cts || !n_keys) { set_err("debug tpke miller: 1..65536 shares, some keys and ciphertexts"); return -1; }
     for (size_t i = 0; i < n; i++)
         if (ct_idx[i] >= n_cts || dec_idx[i] >= n_keys) { set_err("debug tpke miller: index out of range"); return -1; }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const uint8_t *dy = up(c->in[0], y_keys, 48 * n_keys, s);
-    const uint8_t *du = up(c->in[1], cts_u, 48 * n_cts, s);
-    const uint8_t *dw = up(c->in[2], cts_w, 96 * n_cts, s);
-    const uint8_t *dv = up(c->in[3], v_data, (size_t)v_off[n_cts], s);
-    const uint32_t *dvo = up(c->in[4], v_off, n_cts + 1, s);
-    const uint32_t *dct = up(c->in[5], ct_idx, n, s);
-    const uint32_t *ddec = up(c->in[6], dec_idx, n, s);
-    const uint8_t *dui = up(c->in[7], ui, 48 * n, s);
-    uint8_t *dacc = (uint8_t *)c->out[0].get(n);
-    u32 *f = (u32 *)c->t_f.get(n * 576 * (size_t)lcbk_fe_slots());
-    if (!dy || !du || !dw || !dv || !dvo || !dct || !ddec || !dui || !dacc || !f) { set_err("device allocation failed"); return -1; }
+    HostCall h(c, "debug tpke miller");
+    hipStream_t s = h.s;
+    const uint8_t *dy = h.in(y_keys, 48 * n_keys);
+    const uint8_t *du = h.in(cts_u, 48 * n_cts);
+    const uint8_t *dw = h.in(cts_w, 96 * n_cts);
+    const uint8_t *dv = h.in(v_data, (size_t)v_off[n_cts]);
+    const uint32_t *dvo = h.in(v_off, n_cts + 1);
+    const uint32_t *dct = h.in(ct_idx, n);
+    const uint32_t *ddec = h.in(dec_idx, n);
+    const uint8_t *dui = h.in(ui, 48 * n);
+    uint8_t *dacc = h.out<uint8_t>(n);
+    u32 *f = h.out<u32>(n * 144 * (size_t)lcbk_fe_slots());
+    if (!h.ok()) return -1;
     if (tpke_prepare(c, dy, n_keys, du, dw, dv, dvo, n_cts, s)) return -1;
     lcbk_tpke_miller(dim3(nblk(n)), s, (const u32 *)c->t_lines.p, (const uint8_t *)c->t_ctok.p, (u32)n_cts, c->t_keys.p,
                      (u32)n_keys, dct, ddec, dui, (u32)n, f, dacc);
     std::vector<u32> soa((size_t)144 * n);
-    hipMemcpyAsync(soa.data(), f, soa.size() * 4, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(ok_out, dacc, n, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "debug tpke miller")) return -1;
+    h.back(soa.data(), f, soa.size() * 4);
+    h.back(ok_out, dacc, n);
+    if (h.finish()) return -1;
     for (size_t i = 0; i < n; i++)
         for (int w = 0; w < 144; w++) f_out[144 * i + w] = soa[((size_t)(w >> 2) * n + i) * 4 + (w & 3)];
     return 0;
@@ -1065,27 +1059,27 @@ static int tpke_verify_shares_host(uint8_t *accept, size_t n, const uint8_t *y_k
         if (ct_idx[i] >= n_cts) { set_err("ct_idx out of range"); return -1; }
         if (dec_idx[i] >= n_keys) { set_err("dec_idx out of range"); return -1; }
     }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
+    HostCall h(c, "tpke verify");
+    hipStream_t s = h.s;
     size_t vbytes = n_cts ? v_off[n_cts] : 0;
-    const uint8_t *dy = up(c->in[0], y_keys, 48 * n_keys, s);
-    const uint8_t *du = up(c->in[1], cts_u, 48 * n_cts, s);
-    const uint8_t *dw = up(c->in[2], cts_w, 96 * n_cts, s);
-    const uint8_t *dv = up(c->in[3], v_data, vbytes, s);
-    const uint32_t *dvo = up(c->in[4], v_off, n_cts + 1, s);
-    const uint32_t *dct = up(c->in[5], ct_idx, n, s);
-    const uint32_t *ddec = up(c->in[6], dec_idx, n, s);
-    const uint8_t *dui = up(c->in[7], ui, 48 * n, s);
-    uint8_t *dacc = (uint8_t *)c->out[0].get(n);
-    if (!dy || !du || !dw || !dv || !dvo || !dct || !ddec || !dui || !dacc) { set_err("device allocation failed"); return -1; }
+    const uint8_t *dy = h.in(y_keys, 48 * n_keys);
+    const uint8_t *du = h.in(cts_u, 48 * n_cts);
+    const uint8_t *dw = h.in(cts_w, 96 * n_cts);
+    const uint8_t *dv = h.in(v_data, vbytes);
+    const uint32_t *dvo = h.in(v_off, n_cts + 1);
+    const uint32_t *dct = h.in(ct_idx, n);
+    const uint32_t *ddec = h.in(dec_idx, n);
+    const uint8_t *dui = h.in(ui, 48 * n);
+    uint8_t *dacc = h.out<uint8_t>(n);
+    if (!h.ok()) return -1;
     if (batched) {
         if (tpke_verify_shares_rlc_fused(c, dacc, n, dy, n_keys, du, dw, dv, dvo, n_cts, dct, ddec, dui, s)) return -1;
     } else {
         if (tpke_prepare(c, dy, n_keys, du, dw, dv, dvo, n_cts, s)) return -1;
         if (tpke_verify_prepared(c, dacc, n, n_keys, n_cts, dct, ddec, dui, s)) return -1;
     }
-    if (n) hipMemcpyAsync(accept, dacc, n, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "tpke verify") ? 0 : -1;
+    h.back(accept, dacc, n);
+    return h.finish();
 }
 // lcb_tpke_verify_shares with a per-context cache of prepared ciphertexts (the line sets of H and W and the
 // validity, keyed by the ciphertext's bytes, least recently used slot replaced): the protocol verifies the N shares of
@@ -1106,8 +1100,8 @@ extern "C" int lcb_tpke_verify_shares_cached(uint8_t *accept, size_t n, const ui
         if (ct_idx[i] >= n_cts) { set_err("ct_idx out of range"); return -1; }
         if (dec_idx[i] >= n_keys) { set_err("dec_idx out of range"); return -1; }
     }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
+    HostCall h(c, "tpke verify (cached)");
+    hipStream_t s = h.s;
     const int flags = prepare_flags();
     if (c->cc_used.empty() || c->cc_flags != flags) {           // first use, or prepare flags changed: empty cache
         c->cc_map.clear();
@@ -1177,8 +1171,8 @@ extern "C" int lcb_tpke_verify_shares_cached(uint8_t *accept, size_t n, const ui
     // prepare the misses straight into their slots
     if (!kmiss.empty()) {
         const size_t km = kmiss.size() / 48;
-        const uint8_t *dy = up(c->in[0], kmiss.data(), kmiss.size(), s);
-        if (!dy) { set_err("device allocation failed"); return cache_fail(); }
+        const uint8_t *dy = h.in(kmiss.data(), kmiss.size());
+        if (!h.ok()) return cache_fail();
         lcbk_g1_decompress(dim3(nblk(km)), s, dy, (u32)km, (uint8_t *)keys + (size_t)kfirst * LCB_G1A_ST_BYTES);
     }
     if (!miss.empty()) {
@@ -1196,31 +1190,29 @@ extern "C" int lcb_tpke_verify_shares_cached(uint8_t *accept, size_t n, const ui
             msets[2 * j + 1] = 2 * slot_of[k] + 1;
         }
         if (mv.empty()) mv.push_back(0);
-        const uint8_t *du = up(c->in[1], mu.data(), mu.size(), s);
-        const uint8_t *dw = up(c->in[2], mw.data(), mw.size(), s);
-        const uint8_t *dv = up(c->in[3], mv.data(), mv.size(), s);
-        const uint32_t *dvo = up(c->in[4], mvo.data(), mvo.size(), s);
-        const uint32_t *dsl = up(c->sel[0], mslot.data(), m, s);
-        const uint32_t *dse = up(c->sel[1], msets.data(), 2 * m, s);
-        if (!du || !dw || !dv || !dvo || !dsl || !dse || injected(INJ_CT_CACHE_ALLOC)) {
-            set_err("device allocation failed");
-            return cache_fail();
-        }
+        const uint8_t *du = h.in(mu.data(), mu.size());
+        const uint8_t *dw = h.in(mw.data(), mw.size());
+        const uint8_t *dv = h.in(mv.data(), mv.size());
+        const uint32_t *dvo = h.in(mvo.data(), mvo.size());
+        const uint32_t *dsl = h.in(mslot.data(), m);
+        const uint32_t *dse = h.in(msets.data(), 2 * m);
+        if (h.ok() && injected(INJ_CT_CACHE_ALLOC)) h.fail();
+        if (!h.ok()) return cache_fail();
         lcbk_tpke_ct_prepare(dim3(nblk(m)), s, du, dw, dv, dvo, (u32)m, lines, ctok, flags, dsl);
         lines_fill(s, lines, 2 * m, dse, nullptr);
     }
     std::vector<u32> cslot(n);
     for (size_t i = 0; i < n; i++) cslot[i] = slot_of[ct_idx[i]];
-    const uint32_t *dct = up(c->in[5], cslot.data(), n, s);
+    const uint32_t *dct = h.in(cslot.data(), n);
     std::vector<u32> kdec(n);
     for (size_t i = 0; i < n; i++) kdec[i] = kslot[dec_idx[i]];
-    const uint32_t *ddec = up(c->in[6], kdec.data(), n, s);
-    const uint8_t *dui = up(c->in[7], ui, 48 * n, s);
-    uint8_t *dacc = (uint8_t *)c->out[0].get(n);
-    if (!dct || !ddec || !dui || !dacc) { set_err("device allocation failed"); return cache_fail(); }
+    const uint32_t *ddec = h.in(kdec.data(), n);
+    const uint8_t *dui = h.in(ui, 48 * n);
+    uint8_t *dacc = h.out<uint8_t>(n);
+    if (!h.ok()) return cache_fail();
     if (tpke_verify_core(c, lines, ctok, LCB_CT_CACHE, keys, c->kc_n, dacc, n, dct, ddec, dui, s)) return cache_fail();
-    if (n) hipMemcpyAsync(accept, dacc, n, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "tpke verify (cached)")) return cache_fail();
+    h.back(accept, dacc, n);
+    if (h.finish()) return cache_fail();
     return 0;
 }
 extern "C" int lcb_tpke_verify_shares(uint8_t *accept, size_t n, const uint8_t *y_keys, size_t n_keys,
@@ -1243,40 +1235,39 @@ extern "C" int lcb_tpke_partial_decrypt(uint8_t *ui_out, uint8_t *status, const 
                                         size_t n_cts) {
     SYNC_CTX_OR(c, -1)
     if (!n_cts) return 0;
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
+    HostCall h(c, "tpke partial decrypt");
+    hipStream_t s = h.s;
     size_t vbytes = v_off[n_cts];
-    const uint8_t *du = up(c->in[1], cts_u, 48 * n_cts, s);
-    const uint8_t *dw = up(c->in[2], cts_w, 96 * n_cts, s);
-    const uint8_t *dv = up(c->in[3], v_data, vbytes, s);
-    const uint32_t *dvo = up(c->in[4], v_off, n_cts + 1, s);
-    const uint8_t *dx = up(c->in[0], x, 32, s);
-    uint8_t *dui = (uint8_t *)c->out[0].get(48 * n_cts);
-    uint8_t *dst = (uint8_t *)c->out[1].get(n_cts);
-    if (!du || !dw || !dv || !dvo || !dx || !dui || !dst) { set_err("device allocation failed"); return -1; }
+    const uint8_t *du = h.in(cts_u, 48 * n_cts);
+    const uint8_t *dw = h.in(cts_w, 96 * n_cts);
+    const uint8_t *dv = h.in(v_data, vbytes);
+    const uint32_t *dvo = h.in(v_off, n_cts + 1);
+    const uint8_t *dx = h.in(x, 32);
+    uint8_t *dui = h.out<uint8_t>(48 * n_cts);
+    uint8_t *dst = h.out<uint8_t>(n_cts);
+    if (!h.ok()) return -1;
     if (tpke_prepare(c, nullptr, 0, du, dw, dv, dvo, n_cts, s)) return -1;
     if (tpke_partial_decrypt_prepared(c, dui, dst, dx, 0, du, n_cts, s)) return -1;
-    hipMemcpyAsync(ui_out, dui, 48 * n_cts, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(status, dst, n_cts, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "tpke partial decrypt") ? 0 : -1;
+    h.back(ui_out, dui, 48 * n_cts);
+    h.back(status, dst, n_cts);
+    return h.finish();
 }
 
 extern "C" int lcb_tpke_encrypt_phase1(uint8_t *u_out, uint8_t *t_out, const uint8_t y[48], const uint8_t *r, size_t n) {
     SYNC_CTX_OR(c, -1)
     if (!n) return 0;
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const uint8_t *dy = up(c->in[0], y, 48, s);
-    const uint8_t *dr = up(c->in[1], r, 32 * n, s);
-    uint8_t *du = (uint8_t *)c->out[0].get(48 * n), *dt = (uint8_t *)c->out[1].get(48 * n), *dok = (uint8_t *)c->out[2].get(n);
-    u32 *ws = (u32 *)c->lws.get(lcbk_scalar_ws_bytes(3, (u32)n));
-    if (!dy || !dr || !du || !dt || !dok || !ws) { set_err("device allocation failed"); return -1; }
-    lcbk_tpke_encrypt1(s, dy, dr, (u32)n, du, dt, dok, ws);
+    HostCall h(c, "tpke encrypt1");
+    const uint8_t *dy = h.in(y, 48);
+    const uint8_t *dr = h.in(r, 32 * n);
+    uint8_t *du = h.out<uint8_t>(48 * n), *dt = h.out<uint8_t>(48 * n), *dok = h.out<uint8_t>(n);
+    u32 *ws = h.lws(lcbk_scalar_ws_bytes(3, (u32)n));
+    if (!h.ok()) return -1;
+    lcbk_tpke_encrypt1(h.s, dy, dr, (u32)n, du, dt, dok, ws);
     std::vector<uint8_t> ok(n);
-    hipMemcpyAsync(u_out, du, 48 * n, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(t_out, dt, 48 * n, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(ok.data(), dok, n, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "tpke encrypt1")) return -1;
+    h.back(u_out, du, 48 * n);
+    h.back(t_out, dt, 48 * n);
+    h.back(ok.data(), dok, n);
+    if (h.finish()) return -1;
     for (size_t i = 0; i < n; i++) if (!ok[i]) { set_err("invalid public key or scalar"); return -1; }
     return 0;
 }
@@ -1284,19 +1275,18 @@ extern "C" int lcb_tpke_encrypt_phase2(uint8_t *w_out, const uint8_t *u, const u
                                        const uint32_t *v_off, size_t n) {
     SYNC_CTX_OR(c, -1)
     if (!n) return 0;
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const uint8_t *du = up(c->in[0], u, 48 * n, s);
-    const uint8_t *dr = up(c->in[1], r, 32 * n, s);
-    const uint8_t *dv = up(c->in[2], v_data, v_off[n], s);
-    const uint32_t *dvo = up(c->in[3], v_off, n + 1, s);
-    uint8_t *dw = (uint8_t *)c->out[0].get(96 * n), *dok = (uint8_t *)c->out[1].get(n);
-    if (!du || !dr || !dv || !dvo || !dw || !dok) { set_err("device allocation failed"); return -1; }
-    lcbk_tpke_encrypt2(dim3(nblk(n)), s, du, dr, dv, dvo, (u32)n, dw, dok, g_orig_cofactor);
+    HostCall h(c, "tpke encrypt2");
+    const uint8_t *du = h.in(u, 48 * n);
+    const uint8_t *dr = h.in(r, 32 * n);
+    const uint8_t *dv = h.in(v_data, v_off[n]);
+    const uint32_t *dvo = h.in(v_off, n + 1);
+    uint8_t *dw = h.out<uint8_t>(96 * n), *dok = h.out<uint8_t>(n);
+    if (!h.ok()) return -1;
+    lcbk_tpke_encrypt2(dim3(nblk(n)), h.s, du, dr, dv, dvo, (u32)n, dw, dok, g_orig_cofactor);
     std::vector<uint8_t> ok(n);
-    hipMemcpyAsync(w_out, dw, 96 * n, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(ok.data(), dok, n, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "tpke encrypt2")) return -1;
+    h.back(w_out, dw, 96 * n);
+    h.back(ok.data(), dok, n);
+    if (h.finish()) return -1;
     for (size_t i = 0; i < n; i++) if (!ok[i]) { set_err("hash-to-G2 failed"); return -1; }
     return 0;
 }
@@ -1361,25 +1351,25 @@ static int ts_verify_shares_host(uint8_t *accept, size_t n, const uint8_t *pks, 
         if (msg_idx[i] >= n_msgs) { set_err("msg_idx out of range"); return -1; }
         if (pk_idx[i] >= n_pks) { set_err("pk_idx out of range"); return -1; }
     }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
+    HostCall h(c, "ts verify");
+    hipStream_t s = h.s;
     size_t mbytes = n_msgs ? msg_off[n_msgs] : 0;
-    const uint8_t *dpk = up(c->in[0], pks, 48 * n_pks, s);
-    const uint8_t *dsig = up(c->in[1], sigs, 96 * n, s);
-    const uint8_t *dm = up(c->in[2], msg_data, mbytes, s);
-    const uint32_t *dmo = up(c->in[3], msg_off, n_msgs + 1, s);
-    const uint32_t *dmi = up(c->in[4], msg_idx, n, s);
-    const uint32_t *dpi = up(c->in[5], pk_idx, n, s);
-    uint8_t *dacc = (uint8_t *)c->out[0].get(n);
-    if (!dpk || !dsig || !dm || !dmo || !dmi || !dpi || !dacc) { set_err("device allocation failed"); return -1; }
+    const uint8_t *dpk = h.in(pks, 48 * n_pks);
+    const uint8_t *dsig = h.in(sigs, 96 * n);
+    const uint8_t *dm = h.in(msg_data, mbytes);
+    const uint32_t *dmo = h.in(msg_off, n_msgs + 1);
+    const uint32_t *dmi = h.in(msg_idx, n);
+    const uint32_t *dpi = h.in(pk_idx, n);
+    uint8_t *dacc = h.out<uint8_t>(n);
+    if (!h.ok()) return -1;
     if (batched) {
         if (ts_verify_shares_rlc_fused(c, dacc, n, dpk, n_pks, dsig, dm, dmo, n_msgs, dmi, dpi, s)) return -1;
     } else {
         if (ts_prepare(c, dpk, n_pks, dm, dmo, n_msgs, s)) return -1;
         if (ts_verify_prepared(c, dacc, n, n_pks, n_msgs, dsig, dmi, dpi, s)) return -1;
     }
-    if (n) hipMemcpyAsync(accept, dacc, n, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "ts verify") ? 0 : -1;
+    h.back(accept, dacc, n);
+    return h.finish();
 }
 extern "C" int lcb_ts_verify_shares(uint8_t *accept, size_t n, const uint8_t *pks, size_t n_pks, const uint8_t *sigs,
                                     const uint8_t *msg_data, const uint32_t *msg_off, size_t n_msgs,
@@ -1397,19 +1387,18 @@ extern "C" int lcb_ts_sign(uint8_t *sigs_out, const uint8_t *sks, const uint8_t 
     if (!n) return 0;
     u32 nm = 0;
     for (size_t i = 0; i < n; i++) nm = msg_idx[i] + 1 > nm ? msg_idx[i] + 1 : nm;
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const uint8_t *dsk = up(c->in[0], sks, 32 * n, s);
-    const uint8_t *dm = up(c->in[1], msg_data, msg_off[nm], s);
-    const uint32_t *dmo = up(c->in[2], msg_off, nm + 1, s);
-    const uint32_t *dmi = up(c->in[3], msg_idx, n, s);
-    uint8_t *dsig = (uint8_t *)c->out[0].get(96 * n), *dok = (uint8_t *)c->out[1].get(n);
-    if (!dsk || !dm || !dmo || !dmi || !dsig || !dok) { set_err("device allocation failed"); return -1; }
-    lcbk_ts_sign(dim3(nblk(n)), s, dsk, dm, dmo, dmi, (u32)n, dsig, dok, g_orig_cofactor);
+    HostCall h(c, "ts sign");
+    const uint8_t *dsk = h.in(sks, 32 * n);
+    const uint8_t *dm = h.in(msg_data, msg_off[nm]);
+    const uint32_t *dmo = h.in(msg_off, nm + 1);
+    const uint32_t *dmi = h.in(msg_idx, n);
+    uint8_t *dsig = h.out<uint8_t>(96 * n), *dok = h.out<uint8_t>(n);
+    if (!h.ok()) return -1;
+    lcbk_ts_sign(dim3(nblk(n)), h.s, dsk, dm, dmo, dmi, (u32)n, dsig, dok, g_orig_cofactor);
     std::vector<uint8_t> ok(n);
-    hipMemcpyAsync(sigs_out, dsig, 96 * n, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(ok.data(), dok, n, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "ts sign")) return -1;
+    h.back(sigs_out, dsig, 96 * n);
+    h.back(ok.data(), dok, n);
+    if (h.finish()) return -1;
     for (size_t i = 0; i < n; i++) if (!ok[i]) { set_err("invalid key share"); return -1; }
     return 0;
 }
@@ -1439,19 +1428,18 @@ static int lagrange_batch(int g, uint8_t *out, uint8_t *status, const uint8_t *x
                           size_t np) {
     SYNC_CTX_OR(c, -1)
     if (!np) return 0;
-    Enq q(c, c->stream);
+    HostCall h(c, "lagrange");
     size_t ne = off[np];
     size_t pb = g == 1 ? 48 : 96;
-    hipStream_t s = c->stream;
-    const uint8_t *dx = up(c->in[0], xs, 32 * ne, s);
-    const uint8_t *dy = up(c->in[1], ys, pb * ne, s);
-    const uint32_t *doff = up(c->in[2], off, np + 1, s);
-    uint8_t *dst = (uint8_t *)c->out[0].get(np), *dout = (uint8_t *)c->out[1].get(pb * np);
-    if (!dx || !dy || !doff || !dst || !dout) { set_err("device allocation failed"); return -1; }
-    if (lagrange_enqueue(c, g, dout, dst, dx, dy, doff, np, ne, s)) return -1;
-    hipMemcpyAsync(out, dout, pb * np, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(status, dst, np, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "lagrange") ? 0 : -1;
+    const uint8_t *dx = h.in(xs, 32 * ne);
+    const uint8_t *dy = h.in(ys, pb * ne);
+    const uint32_t *doff = h.in(off, np + 1);
+    uint8_t *dst = h.out<uint8_t>(np), *dout = h.out<uint8_t>(pb * np);
+    if (!h.ok()) return -1;
+    if (lagrange_enqueue(c, g, dout, dst, dx, dy, doff, np, ne, h.s)) return -1;
+    h.back(out, dout, pb * np);
+    h.back(status, dst, np);
+    return h.finish();
 }
 extern "C" int lcb_ctx_g1_lagrange_dev(lcb_ctx *ctx, uint8_t *out, uint8_t *status, const uint8_t *xs, const uint8_t *ys,
                                        const uint32_t *off, size_t n_problems, size_t n_entries, void *stream) {
@@ -1482,20 +1470,20 @@ static int mul_batch(int g, uint8_t *out, const uint8_t *points, int use_gen, co
     SYNC_CTX_OR(c, -1)
     if (!n) return 0;
     if (n > 0xffffffffu) { set_err("mul batch: too large"); return -1; }
-    Enq q(c, c->stream);
+    HostCall h(c, "mul batch");
     size_t pb = g == 1 ? 48 : 96;
-    hipStream_t s = c->stream;
-    const uint8_t *dp = use_gen ? (const uint8_t *)c->in[0].get(16) : up(c->in[0], points, pb * n, s);
-    const uint8_t *dsc = up(c->in[1], scalars, 32 * n, s);
-    uint8_t *dout = (uint8_t *)c->out[0].get(pb * n), *dok = (uint8_t *)c->out[1].get(n);
-    u32 *ws = (u32 *)c->lws.get(lcbk_scalar_ws_bytes(g, (u32)n));
-    if (!dp || !dsc || !dout || !dok || !ws) { set_err("device allocation failed"); return -1; }
+    hipStream_t s = h.s;
+    const uint8_t *dp = use_gen ? h.out<uint8_t>(16) : h.in(points, pb * n);
+    const uint8_t *dsc = h.in(scalars, 32 * n);
+    uint8_t *dout = h.out<uint8_t>(pb * n), *dok = h.out<uint8_t>(n);
+    u32 *ws = h.lws(lcbk_scalar_ws_bytes(g, (u32)n));
+    if (!h.ok()) return -1;
     if (g == 1) lcbk_g1_mul(s, dp, use_gen, dsc, (u32)n, dout, dok, ws);
     else lcbk_g2_mul(s, dp, use_gen, dsc, (u32)n, dout, dok, ws);
     std::vector<uint8_t> ok(n);
-    hipMemcpyAsync(out, dout, pb * n, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(ok.data(), dok, n, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "mul batch")) return -1;
+    h.back(out, dout, pb * n);
+    h.back(ok.data(), dok, n);
+    if (h.finish()) return -1;
     for (size_t i = 0; i < n; i++) if (!ok[i]) { set_err("invalid point or scalar"); return -1; }
     return 0;
 }
@@ -1508,17 +1496,16 @@ extern "C" int lcb_g2_mul_batch(uint8_t *out, const uint8_t *points, int gen, co
 extern "C" int lcb_g2_hash_batch(uint8_t *out, const uint8_t *msg_data, const uint32_t *msg_off, size_t n) {
     SYNC_CTX_OR(c, -1)
     if (!n) return 0;
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const uint8_t *dm = up(c->in[0], msg_data, msg_off[n], s);
-    const uint32_t *dmo = up(c->in[1], msg_off, n + 1, s);
-    uint8_t *dout = (uint8_t *)c->out[0].get(96 * n), *dok = (uint8_t *)c->out[1].get(n);
-    if (!dm || !dmo || !dout || !dok) { set_err("device allocation failed"); return -1; }
-    lcbk_g2_hash(dim3(nblk(n)), s, dm, dmo, (u32)n, dout, dok, g_orig_cofactor);
+    HostCall h(c, "hash batch");
+    const uint8_t *dm = h.in(msg_data, msg_off[n]);
+    const uint32_t *dmo = h.in(msg_off, n + 1);
+    uint8_t *dout = h.out<uint8_t>(96 * n), *dok = h.out<uint8_t>(n);
+    if (!h.ok()) return -1;
+    lcbk_g2_hash(dim3(nblk(n)), h.s, dm, dmo, (u32)n, dout, dok, g_orig_cofactor);
     std::vector<uint8_t> ok(n);
-    hipMemcpyAsync(out, dout, 96 * n, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(ok.data(), dok, n, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "hash batch")) return -1;
+    h.back(out, dout, 96 * n);
+    h.back(ok.data(), dok, n);
+    if (h.finish()) return -1;
     for (size_t i = 0; i < n; i++) if (!ok[i]) { set_err("hash-to-G2 failed"); return -1; }
     return 0;
 }
@@ -1571,7 +1558,7 @@ extern "C" int lcb_ctx_g1_jac_sum_dev(lcb_ctx *ctx, uint8_t *out48, void *out_ja
         lcbk_g1_jac_compress(dim3(1), q.s, parts, 1, out48);
         return launch_ok("jac sum launch") ? 0 : -1;
     }
-    void *acc = out_jac ? out_jac : c->msm[14].get(LCB_G1_JAC_BYTES);
+    void *acc = out_jac ? out_jac : c->msm[MSM_JAC_SUM].get(LCB_G1_JAC_BYTES);
     if (!acc) { set_err("device allocation failed"); return -1; }
     lcbk_g1_jac_reduce_groups(dim3(1), q.s, parts, (u32)k, k ? (u32)k : 1u, acc);
     if (out48) lcbk_g1_jac_compress(dim3(1), q.s, acc, 1, out48);
@@ -1595,21 +1582,21 @@ extern "C" int lcb_g1_msm(uint8_t out[48], const uint8_t *points, const uint8_t 
         const uint8_t *sc = scalars + 32 * i;
         if (!fr_bytes_lt_r(sc)) { set_err("invalid point or scalar"); return -1; }
     }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const uint8_t *dp = up(c->in[0], points, 48 * n, s);
-    const uint8_t *dsc = up(c->in[1], scalars, 32 * n, s);
-    void *aff = c->in[2].get(96 * n);
-    uint8_t *dok = (uint8_t *)c->out[0].get(n), *dout = (uint8_t *)c->out[1].get(48);
-    void *jac = c->out[2].get(LCB_G1_JAC_BYTES);
-    if (!dp || !dsc || !aff || !dok || !dout || !jac) { set_err("device allocation failed"); return -1; }
+    HostCall h(c, "msm");
+    hipStream_t s = h.s;
+    const uint8_t *dp = h.in(points, 48 * n);
+    const uint8_t *dsc = h.in(scalars, 32 * n);
+    void *aff = h.out<uint8_t>(96 * n);
+    uint8_t *dok = h.out<uint8_t>(n), *dout = h.out<uint8_t>(48);
+    void *jac = h.out<uint8_t>(LCB_G1_JAC_BYTES);
+    if (!h.ok()) return -1;
     lcbk_g1_to_affine(dim3(nblk(n)), s, dp, (u32)n, aff, dok);
     if (msm_enqueue(c, jac, aff, dsc, n, 0, s)) return -1;
     lcbk_g1_jac_compress(dim3(1), s, jac, 1, dout);
     std::vector<uint8_t> ok(n);
-    hipMemcpyAsync(out, dout, 48, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(ok.data(), dok, n, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "msm")) return -1;
+    h.back(out, dout, 48);
+    h.back(ok.data(), dok, n);
+    if (h.finish()) return -1;
     for (size_t i = 0; i < n; i++) if (!ok[i]) { set_err("invalid point or scalar"); return -1; }
     return 0;
 }

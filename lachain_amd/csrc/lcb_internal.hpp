@@ -1,5 +1,5 @@
 // lachain_amd/csrc/lcb_internal.hpp — the few host internals the host files share: what lcb_host.cpp gives every
-// feature file (error slot, device, context resolution, launch / synchronisation checks, uploads, fault injection),
+// feature file (error slot, device, context resolution, launch / synchronisation checks, fault injection),
 // what the batch-check driver (lcb_batch.cpp) and the mcl surface (lcb_mcl.cpp) need from the exact paths in
 // lcb_host.cpp, and the driver calls lcb_host.cpp's host-pointer entry points make.  Not part of the C ABI.
 #pragma once
@@ -22,11 +22,6 @@ bool sync_check(lcb_ctx *c, const char *what);   // the same, then the context's
 #define SYNC_CTX_OR(var, ret)                    \
     lcb_ctx *var = ctx_sync();                   \
     if (!var) return ret;
-template <class T> T *up(DevBuf &b, const T *src, size_t count, hipStream_t s) {
-    T *d = (T *)b.get(count * sizeof(T));
-    if (d && count) hipMemcpyAsync(d, src, count * sizeof(T), hipMemcpyHostToDevice, s);
-    return d;
-}
 inline uint32_t nblk(size_t n) { return (uint32_t)((n + 255) / 256); }   // blocks of 256 lanes
 // fault injection (lcb_test_inject_failure, LCB_ALLOW_TEST_HOOKS=1): the next `count` passes through site `site` fail
 enum { INJ_STAGE_HOST_ALLOC = 1, INJ_CT_CACHE_ALLOC = 2, INJ_PAIRING_ALLOC = 3, INJ_STAGE_OP = 4 };
@@ -68,3 +63,5 @@ int ts_verify_shares_rlc_fused(lcb_ctx *c, uint8_t *d_accept, size_t n, const ui
 
 // ---- lcb_mcl.cpp, for lcb_host.cpp (at global scope, as it always was: the library's unmangled exports stay the same)
 extern std::atomic<int> g_g2_sign_b;        // lcb_set_g2_sign_from_b: lcb_test_linesets decodes its points with it too
+
+#include "host_call.hpp"                    // HostCall: the scope and staging slots of a host-pointer entry point

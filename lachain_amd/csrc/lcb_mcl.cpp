@@ -756,8 +756,8 @@ extern "C" void mclBn_pairing(mclBnGT *z, const mclBnG1 *x, const mclBnG2 *y) {
     fail_out(z, 576);                  // overwritten on success; a failed call leaves a value no other call produces
     if (injected(INJ_PAIRING_ALLOC)) { set_err("injected failure (pairing)"); return; }
     SYNC_CTX_OR(c, )
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
+    HostCall h(c, "pairing");
+    hipStream_t s = h.s;
     const size_t slots = lcbk_fe_slots() > 6 ? (size_t)lcbk_fe_slots() : 6;
     // the group record (P and infinity, then the check's descriptor), staged in one copy
     struct PairIn {
@@ -765,11 +765,12 @@ extern "C" void mclBn_pairing(mclBnGT *z, const mclBnG1 *x, const mclBnG2 *y) {
         uint32_t desc[4];
     };
     static_assert(sizeof(PairIn) == 2 * LCB_G1A_ST_BYTES + 16, "PairIn layout");
-    uint8_t *gin = (uint8_t *)c->mcl[1].get(sizeof(PairIn));
+    uint8_t *gin = h.out<uint8_t>(sizeof(PairIn));
+    u32 *park = h.out<u32>(144 * slots);
+    uint8_t *fl = h.out<uint8_t>(64);
+    if (!h.ok()) return;
     u32 *lines = (u32 *)c->pc_lines.get((size_t)2 * LCB_PAIR_CACHE * LCB_LINESET_BYTES);
-    u32 *park = (u32 *)c->mcl[4].get(576 * slots);
-    uint8_t *fl = (uint8_t *)c->mcl[5].get(64);
-    if (!gin || !lines || !park || !fl) { set_err("device allocation failed"); return; }
+    if (!lines) { set_err("device allocation failed"); return; }
     void *gpts = gin, *desc = gin + 2 * LCB_G1A_ST_BYTES;
     if (c->pc_used.empty()) {
         c->pc_keys.assign((size_t)72 * LCB_PAIR_CACHE, 0);
@@ -838,8 +839,8 @@ extern "C" void mclBn_pairing(mclBnGT *z, const mclBnG1 *x, const mclBnG2 *y) {
     lcbk_coop_tpke_miller(s, lines, desc, gpts, 1, park, fl, fl + 32, 1, 1);
     lcbk_coop_final_exp_check(s, park, 1, nullptr);
     u32 r[144];
-    hipMemcpyAsync(r, park, 576, hipMemcpyDeviceToHost, s);
-    if (sync_check(c, "pairing")) memcpy(z, r, 576);
+    h.back(r, park, 576);
+    if (!h.finish()) memcpy(z, r, 576);
     else c->pc_used[slot] = 0;                    // the slot's lines may be incomplete
 }
 // mclBn_finalExp on the nine-lane kernel (park slot 0 of a one-value workspace)
@@ -848,16 +849,16 @@ extern "C" void mclBn_finalExp(mclBnGT *y, const mclBnGT *x) {
     x = &xin;
     fail_out(y, 576);
     SYNC_CTX_OR(c, )
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
+    HostCall h(c, "final exp");
+    hipStream_t s = h.s;
     const size_t slots = lcbk_fe_slots() > 6 ? (size_t)lcbk_fe_slots() : 6;
-    u32 *park = (u32 *)c->mcl[4].get(576 * slots);
-    if (!park) { set_err("device allocation failed"); return; }
-    hipMemcpyAsync(park, x, 576, hipMemcpyHostToDevice, s);
+    u32 *park = h.out<u32>(144 * slots);
+    if (!h.ok()) return;
+    hipMemcpyAsync(park, x, 576, hipMemcpyHostToDevice, s);    // slot 0 of the park workspace
     lcbk_coop_final_exp_check(s, park, 1, nullptr);
     u32 r[144];
-    hipMemcpyAsync(r, park, 576, hipMemcpyDeviceToHost, s);
-    if (sync_check(c, "final exp")) memcpy(y, r, 576);
+    h.back(r, park, 576);
+    if (!h.finish()) memcpy(y, r, 576);
 }
 // sum_i [k_i] x_i (canonical scalars k_i < r, raw words) on the cooperative ladders of mclBnG1_mul: three groups per
 // term (GLV halves over P and phi(P), and [z^2] P for the membership the split needs), k_ptmul_g1_multi, the terms
@@ -895,15 +896,14 @@ static int g1_mulvec_coop(lcb_ctx *c, mclBnG1 *z, const mclBnG1 *x, const uint64
         if (!put_digits(J[0], k1, 3, 33) || !put_digits(J[1], k2, 2, 33) || !put_digits(J[2], z2, 2, 33)) return 0;
         live[i] = 1;
     }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const void *dj = up(c->mcl[8], (const u32 *)jobs.data(), jobs.size() * sizeof(PtJobG1) / 4, s);
-    void *dout = c->mcl[9].get(3 * n * sizeof(fph::g1));
-    if (!dj || !dout) { set_err("device allocation failed"); return -1; }
-    lcbk_ptmul_g1_multi(s, dj, (u32)(3 * n), dout);
+    HostCall h(c, "mulVec");
+    const PtJobG1 *dj = h.in(jobs.data(), jobs.size());
+    fph::g1 *dout = h.out<fph::g1>(3 * n);
+    if (!h.ok()) return -1;
+    lcbk_ptmul_g1_multi(h.s, dj, (u32)(3 * n), dout);
     std::vector<fph::g1> acc(3 * n);
-    hipMemcpyAsync(acc.data(), dout, 3 * n * sizeof(fph::g1), hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "mulVec")) return -1;
+    h.back(acc.data(), dout, 3 * n * sizeof(fph::g1));
+    if (h.finish()) return -1;
     fph::g1 r;
     fph::jac_set_inf(r);
     for (size_t i = 0; i < n; i++) {
@@ -960,15 +960,14 @@ static int g2_terms_coop(lcb_ctx *c, mclBnG2 *z, const mclBnG2 *x, const uint64_
         if (!ok) return 0;
         live[i] = 1;
     }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const void *dj = up(c->mcl[8], (const u32 *)jobs.data(), jobs.size() * sizeof(PtJobG2) / 4, s);
-    void *dout = c->mcl[9].get(5 * n * sizeof(fph::g2));
-    if (!dj || !dout) { set_err("device allocation failed"); return -1; }
-    lcbk_ptmul_g2_multi(s, dj, (u32)(5 * n), dout);
+    HostCall h(c, "G2 terms");
+    const PtJobG2 *dj = h.in(jobs.data(), jobs.size());
+    fph::g2 *dout = h.out<fph::g2>(5 * n);
+    if (!h.ok()) return -1;
+    lcbk_ptmul_g2_multi(h.s, dj, (u32)(5 * n), dout);
     std::vector<fph::g2> acc(5 * n);
-    hipMemcpyAsync(acc.data(), dout, 5 * n * sizeof(fph::g2), hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "G2 terms")) return -1;
+    h.back(acc.data(), dout, 5 * n * sizeof(fph::g2));
+    if (h.finish()) return -1;
     fph::g2 r;
     fph::jac_set_inf(r);
     for (size_t i = 0; i < n; i++) {
@@ -1018,15 +1017,15 @@ static bool g1_mulvec(mclBnG1 *z, const mclBnG1 *x, const mclBnFr *y, mclSize n)
         const int rc = g1_mulvec_coop(c, z, x, (const uint64_t (*)[4])raw.data(), n);
         if (rc != 0) return rc > 0;
     }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const u32 *pts = up(c->mcl[0], (const u32 *)x, 36 * n, s);
-    const uint64_t *sc = up(c->mcl[1], raw.data(), 4 * n, s);
-    uint8_t *terms = (uint8_t *)c->mcl[2].get(LCB_G1_JAC_BYTES * n);
-    uint8_t *tmp = (uint8_t *)c->mcl[3].get(LCB_G1_JAC_BYTES * ((n + 255) / 256));
-    uint8_t *dz = (uint8_t *)c->mcl[5].get(LCB_G1_JAC_BYTES);
-    u32 *ws = (u32 *)c->lws.get(lcbk_mcl_terms_ws_bytes((u32)n));
-    if (!pts || !sc || !terms || !tmp || !dz || !ws) { set_err("device allocation failed"); return false; }
+    HostCall h(c, "mulVec");
+    hipStream_t s = h.s;
+    const u32 *pts = h.in((const u32 *)x, 36 * n);
+    const uint64_t *sc = h.in(raw.data(), 4 * n);
+    uint8_t *terms = h.out<uint8_t>(LCB_G1_JAC_BYTES * n);
+    uint8_t *tmp = h.out<uint8_t>(LCB_G1_JAC_BYTES * ((n + 255) / 256));
+    uint8_t *dz = h.out<uint8_t>(LCB_G1_JAC_BYTES);
+    u32 *ws = h.lws(lcbk_mcl_terms_ws_bytes((u32)n));
+    if (!h.ok()) return false;
     lcbk_mcl_g1_terms(s, pts, sc, (u32)n, terms, ws);
     uint8_t *cur = terms;
     size_t cnt = n;
@@ -1038,8 +1037,8 @@ static bool g1_mulvec(mclBnG1 *z, const mclBnG1 *x, const mclBnFr *y, mclSize n)
     }
     lcbk_mcl_g1_sum(s, cur, (u32)cnt, dz);
     mclBnG1 r;
-    hipMemcpyAsync(&r, dz, 144, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "mulVec")) return false;
+    h.back(&r, dz, 144);
+    if (h.finish()) return false;
     *z = r;
     return true;
 }
@@ -1057,25 +1056,25 @@ static int lagrange_points(int g, void *out, const mclBnFr *xVec, const void *yV
     std::vector<uint64_t> xs(4 * k);
     for (size_t i = 0; i < k; i++) frh::to_raw(&xs[4 * i], FRV(&xVec[i]));
     const uint32_t off[2] = {0, (uint32_t)k};
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const uint8_t *dx = (const uint8_t *)up(c->mcl[0], xs.data(), 4 * k, s);
-    const u32 *dyr = up(c->mcl[1], (const u32 *)yVec, words * k, s);
-    const uint32_t *doff = up(c->mcl[2], off, 2, s);
-    uint8_t *dy = (uint8_t *)c->mcl[3].get(pb * k);
-    uint8_t *dst = (uint8_t *)c->mcl[4].get(16), *dout = (uint8_t *)c->mcl[5].get(pb);
-    u32 *rec = (u32 *)c->mcl[6].get(words * 4);
-    uint8_t *dok = (uint8_t *)c->mcl[7].get(16);
-    if (!dx || !dyr || !doff || !dy || !dst || !dout || !rec || !dok) { set_err("device allocation failed"); return -1; }
+    HostCall h(c, "lagrange");
+    hipStream_t s = h.s;
+    const uint8_t *dx = (const uint8_t *)h.in(xs.data(), 4 * k);
+    const u32 *dyr = h.in((const u32 *)yVec, words * k);
+    const uint32_t *doff = h.in(off, 2);
+    uint8_t *dy = h.out<uint8_t>(pb * k);
+    uint8_t *dst = h.out<uint8_t>(16), *dout = h.out<uint8_t>(pb);
+    u32 *rec = h.out<u32>(words);
+    uint8_t *dok = h.out<uint8_t>(16);
+    if (!h.ok()) return -1;
     lcbk_mcl_to_bytes(s, g, dyr, (u32)k, dy);
     if (lagrange_enqueue(c, g, dout, dst, dx, dy, doff, 1, k, s)) return -1;
     lcbk_mcl_from_bytes(s, g, dout, 1, rec, dok);
     u32 r[72];
     uint8_t st = 0, ok = 0;
-    hipMemcpyAsync(r, rec, words * 4, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(&st, dst, 1, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(&ok, dok, 1, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "lagrange") || !st || !ok) return -1;
+    h.back(r, rec, words * 4);
+    h.back(&st, dst, 1);
+    h.back(&ok, dok, 1);
+    if (h.finish() || !st || !ok) return -1;
     memcpy(out, r, words * 4);
     return 0;
 }
@@ -1158,15 +1157,15 @@ static int eval_poly_g1_terms(lcb_ctx *c, mclBnG1 *out, const mclBnG1 *coef, siz
         if (i) ne_mulmod(e, e, xr);
         memcpy(&sc[12 * i], e, 48);
     }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const u32 *pts = up(c->mcl[0], (const u32 *)coef, 36 * n, s);
-    const u32 *dsc = up(c->mcl[1], sc.data(), 12 * n, s);
-    uint8_t *terms = (uint8_t *)c->mcl[2].get(LCB_G1_JAC_BYTES * n);
-    uint8_t *tmp = (uint8_t *)c->mcl[3].get(LCB_G1_JAC_BYTES * ((n + 255) / 256));
-    uint8_t *dz = (uint8_t *)c->mcl[5].get(LCB_G1_JAC_BYTES);
-    u32 *ws = (u32 *)c->lws.get(lcbk_mcl_terms_wide_ws_bytes((u32)n));
-    if (!pts || !dsc || !terms || !tmp || !dz || !ws) { set_err("device allocation failed"); return -1; }
+    HostCall h(c, "evaluate polynomial");
+    hipStream_t s = h.s;
+    const u32 *pts = h.in((const u32 *)coef, 36 * n);
+    const u32 *dsc = h.in(sc.data(), 12 * n);
+    uint8_t *terms = h.out<uint8_t>(LCB_G1_JAC_BYTES * n);
+    uint8_t *tmp = h.out<uint8_t>(LCB_G1_JAC_BYTES * ((n + 255) / 256));
+    uint8_t *dz = h.out<uint8_t>(LCB_G1_JAC_BYTES);
+    u32 *ws = h.lws(lcbk_mcl_terms_wide_ws_bytes((u32)n));
+    if (!h.ok()) return -1;
     lcbk_mcl_g1_terms_wide(s, pts, dsc, (u32)n, terms, ws);
     uint8_t *cur = terms;
     size_t cnt = n;
@@ -1178,8 +1177,8 @@ static int eval_poly_g1_terms(lcb_ctx *c, mclBnG1 *out, const mclBnG1 *coef, siz
     }
     lcbk_mcl_g1_sum(s, cur, (u32)cnt, dz);
     mclBnG1 r;
-    hipMemcpyAsync(&r, dz, 144, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "evaluate polynomial")) return -1;
+    h.back(&r, dz, 144);
+    if (h.finish()) return -1;
     *out = r;
     return 0;
 }
@@ -1219,16 +1218,15 @@ static int eval_poly(int g, void *out, const void *coef, mclSize n, const mclBnF
         const int rc = g2_terms_coop(c, (mclBnG2 *)out, (const mclBnG2 *)coef, (const uint64_t (*)[4])raw.data(), n);
         if (rc != 0) return rc > 0 ? 0 : -1;
     }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const u32 *dc = up(c->mcl[0], (const u32 *)coef, words * n, s);
-    const uint64_t *dx = up(c->mcl[1], xr, 4, s);
-    u32 *dout = (u32 *)c->mcl[2].get(words * 4);
-    if (!dc || !dx || !dout) { set_err("device allocation failed"); return -1; }
-    lcbk_mcl_horner(s, g, dc, (u32)n, dx, dout);
+    HostCall h(c, "evaluate polynomial");
+    const u32 *dc = h.in((const u32 *)coef, words * n);
+    const uint64_t *dx = h.in(xr, 4);
+    u32 *dout = h.out<u32>(words);
+    if (!h.ok()) return -1;
+    lcbk_mcl_horner(h.s, g, dc, (u32)n, dx, dout);
     u32 r[72];
-    hipMemcpyAsync(r, dout, words * 4, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "evaluate polynomial")) return -1;
+    h.back(r, dout, words * 4);
+    if (h.finish()) return -1;
     memcpy(out, r, words * 4);
     return 0;
 }

@@ -31,11 +31,6 @@ int depth_of(int n) {
     while ((1 << d) < n) d++;
     return d;
 }
-bool monotone(const uint64_t *off, size_t n, const char *what) {
-    for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) { set_err(what); return false; }
-    return true;
-}
 void rs_matrix_lds() {
     static bool attr = false;
     if (attr) return;
@@ -68,9 +63,9 @@ extern "C" int lcb_rbc_val_batch(uint8_t *shards_out, uint8_t *roots_out, uint8_
     if (n < 1 || n > 256 || f < 0 || n - 2 * f <= 0) { set_err("rbc val: need 1 <= n <= 256 and 0 <= 2f < n"); return -1; }
     if (!B) return 0;
     if (B > MAX_BATCH) { set_err("rbc val: at most 65535 instances per call"); return -1; }
-    if (!monotone(payload_off, B, "rbc val: offsets must not decrease")) return -1;
+    std::vector<uint64_t> poff, soff(B + 1);
+    if (!rebase(poff, payload_off, B, "rbc val: offsets must not decrease")) return -1;
     const int k = n - 2 * f, m = 2 * f, depth = depth_of(n);
-    std::vector<uint64_t> poff(B + 1), soff(B + 1);
     size_t max_S = 0;
     soff[0] = 0;
     for (size_t b = 0; b < B; b++) {
@@ -80,21 +75,17 @@ extern "C" int lcb_rbc_val_batch(uint8_t *shards_out, uint8_t *roots_out, uint8_
         max_S = S > max_S ? S : max_S;
         soff[b + 1] = soff[b] + (uint64_t)n * S;
     }
-    for (size_t b = 0; b <= B; b++) poff[b] = payload_off[b] - payload_off[0];
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const uint8_t *dpay = up(c->rbc[0], payloads + payload_off[0], (size_t)poff[B], s);
-    const uint64_t *dpoff = up(c->rbc[1], poff.data(), B + 1, s);
-    const uint64_t *dsoff = up(c->rbc[2], soff.data(), B + 1, s);
-    uint8_t *dsh = (uint8_t *)c->rbc[3].get((size_t)soff[B]);
-    int *dpos = (int *)c->rbc[4].get(4 * (size_t)n);
-    uint8_t *dM = (uint8_t *)c->rbc[5].get((size_t)m * k + 16);
-    uint8_t *droots = (uint8_t *)c->rbc[7].get(32 * B);
-    uint8_t *dproofs = (uint8_t *)c->rbc[8].get(32 * B * n * (size_t)depth);
-    if (!dpay || !dpoff || !dsoff || !dsh || !dpos || !dM || !droots || !dproofs) {
-        set_err("device allocation failed");
-        return -1;
-    }
+    HostCall h(c, "rbc val");
+    hipStream_t s = h.s;
+    const uint8_t *dpay = h.in(payloads + payload_off[0], (size_t)poff[B]);
+    const uint64_t *dpoff = h.in(poff.data(), B + 1);
+    const uint64_t *dsoff = h.in(soff.data(), B + 1);
+    uint8_t *dsh = h.out<uint8_t>((size_t)soff[B]);
+    int *dpos = h.out<int>((size_t)n);
+    uint8_t *dM = h.out<uint8_t>((size_t)m * k + 16);
+    uint8_t *droots = h.out<uint8_t>(32 * B);
+    uint8_t *dproofs = h.out<uint8_t>(32 * B * n * (size_t)depth);
+    if (!h.ok()) return -1;
     lcbk_rbc_augment(s, dpay, dpoff, dsh, dsoff, n, k, max_S * k, (unsigned)B);
     uint8_t *dok = dM + (size_t)m * k;
     uint8_t ok = 1;
@@ -110,10 +101,10 @@ extern "C" int lcb_rbc_val_batch(uint8_t *shards_out, uint8_t *roots_out, uint8_
     }
     lcbk_rbc_tree(s, dsh, dsoff, n, depth, nullptr, droots, depth ? dproofs : nullptr, (unsigned)B);
     if (!launch_ok("rbc val launch")) return -1;
-    if (shards_out) hipMemcpyAsync(shards_out, dsh, (size_t)soff[B], hipMemcpyDeviceToHost, s);
-    if (roots_out) hipMemcpyAsync(roots_out, droots, 32 * B, hipMemcpyDeviceToHost, s);
-    if (proofs_out && depth) hipMemcpyAsync(proofs_out, dproofs, 32 * B * n * (size_t)depth, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "rbc val")) return -1;
+    h.back(shards_out, dsh, (size_t)soff[B]);
+    h.back(roots_out, droots, 32 * B);
+    h.back(proofs_out, dproofs, 32 * B * n * (size_t)depth);
+    if (h.finish()) return -1;
     if (!ok) { set_err("rbc val: parity positions are not independent"); return -1; }
     return 0;
 }
@@ -145,24 +136,22 @@ extern "C" int lcb_rbc_check_echo_batch(uint8_t *accept, const uint8_t *data, co
     if (!shards_ok(n_shards, "rbc check echo: need 1 <= n_shards <= 256")) return -1;
     if (!n_items) return 0;
     if (n_items > MAX_ITEMS) { set_err("rbc check echo: batch too large"); return -1; }
-    if (!monotone(data_off, n_items, "rbc check echo: data offsets must not decrease") ||
-        !monotone(proof_off, n_items, "rbc check echo: proof offsets must not decrease"))
+    std::vector<uint64_t> doff, poff;
+    if (!rebase(doff, data_off, n_items, "rbc check echo: data offsets must not decrease") ||
+        !rebase(poff, proof_off, n_items, "rbc check echo: proof offsets must not decrease"))
         return -1;
-    std::vector<uint64_t> doff(n_items + 1), poff(n_items + 1);
-    for (size_t i = 0; i <= n_items; i++) { doff[i] = data_off[i] - data_off[0]; poff[i] = proof_off[i] - proof_off[0]; }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const uint8_t *dd = up(c->rbc[0], data + data_off[0], (size_t)doff[n_items], s);
-    const uint64_t *ddoff = up(c->rbc[1], doff.data(), n_items + 1, s);
-    const uint64_t *dpoff = up(c->rbc[2], poff.data(), n_items + 1, s);
-    const int32_t *dfrom = up(c->rbc[4], from, n_items, s);
-    const uint8_t *dpr = up(c->rbc[10], proofs + 32 * proof_off[0], 32 * (size_t)poff[n_items], s);
-    const uint8_t *droots = up(c->rbc[11], roots, 32 * n_items, s);
-    uint8_t *dacc = (uint8_t *)c->rbc[9].get(n_items);
-    if (!dd || !ddoff || !dpoff || !dfrom || !dpr || !droots || !dacc) { set_err("device allocation failed"); return -1; }
-    if (lcb_ctx_rbc_check_echo_dev(c, dacc, dd, ddoff, dfrom, droots, dpr, dpoff, n_items, n_shards, s)) return -1;
-    hipMemcpyAsync(accept, dacc, n_items, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "rbc check echo") ? 0 : -1;
+    HostCall h(c, "rbc check echo");
+    const uint8_t *dd = h.in(data + data_off[0], (size_t)doff[n_items]);
+    const uint64_t *ddoff = h.in(doff.data(), n_items + 1);
+    const uint64_t *dpoff = h.in(poff.data(), n_items + 1);
+    const int32_t *dfrom = h.in(from, n_items);
+    const uint8_t *dpr = h.in(proofs + 32 * proof_off[0], 32 * (size_t)poff[n_items]);
+    const uint8_t *droots = h.in(roots, 32 * n_items);
+    uint8_t *dacc = h.out<uint8_t>(n_items);
+    if (!h.ok()) return -1;
+    if (lcb_ctx_rbc_check_echo_dev(c, dacc, dd, ddoff, dfrom, droots, dpr, dpoff, n_items, n_shards, h.s)) return -1;
+    h.back(accept, dacc, n_items);
+    return h.finish();
 }
 
 // ------------------------------------------------------------------ ConstructMerkleTree
@@ -189,24 +178,22 @@ extern "C" int lcb_rbc_merkle_tree_batch(uint8_t *trees_out, const uint8_t *shar
     if (!shards_ok(n_shards, "rbc merkle tree: need 1 <= n_shards <= 256")) return -1;
     if (!B) return 0;
     if (B > MAX_ITEMS) { set_err("rbc merkle tree: batch too large"); return -1; }
-    if (!monotone(shard_off, B, "rbc merkle tree: offsets must not decrease")) return -1;
-    std::vector<uint64_t> off(B + 1);
-    for (size_t b = 0; b <= B; b++) off[b] = shard_off[b] - shard_off[0];
+    std::vector<uint64_t> off;
+    if (!rebase(off, shard_off, B, "rbc merkle tree: offsets must not decrease")) return -1;
     for (size_t b = 0; b < B; b++)
         if ((off[b + 1] - off[b]) % (uint64_t)n_shards) {
             set_err("rbc merkle tree: an instance's bytes are not n_shards equal shards");
             return -1;
         }
     const size_t tree_bytes = 64 * ((size_t)1 << depth_of(n_shards));
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const uint8_t *dsh = up(c->rbc[0], shards + shard_off[0], (size_t)off[B], s);
-    const uint64_t *doff = up(c->rbc[1], off.data(), B + 1, s);
-    uint8_t *dtrees = (uint8_t *)c->rbc[8].get(tree_bytes * B);
-    if (!dsh || !doff || !dtrees) { set_err("device allocation failed"); return -1; }
-    if (lcb_ctx_rbc_merkle_tree_dev(c, dtrees, dsh, doff, B, n_shards, s)) return -1;
-    hipMemcpyAsync(trees_out, dtrees, tree_bytes * B, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "rbc merkle tree") ? 0 : -1;
+    HostCall h(c, "rbc merkle tree");
+    const uint8_t *dsh = h.in(shards + shard_off[0], (size_t)off[B]);
+    const uint64_t *doff = h.in(off.data(), B + 1);
+    uint8_t *dtrees = h.out<uint8_t>(tree_bytes * B);
+    if (!h.ok()) return -1;
+    if (lcb_ctx_rbc_merkle_tree_dev(c, dtrees, dsh, doff, B, n_shards, h.s)) return -1;
+    h.back(trees_out, dtrees, tree_bytes * B);
+    return h.finish();
 }
 
 // ------------------------------------------------------------------ TrySendReadyMessageFromEchos
@@ -219,12 +206,11 @@ extern "C" int lcb_rbc_decode_batch(uint8_t *shards_out, uint8_t *status, uint8_
     if (!B) return 0;
     if (B > MAX_BATCH) { set_err("rbc decode: at most 65535 instances per call"); return -1; }
     if (!status) { set_err("rbc decode: status is required"); return -1; }
-    if (!monotone(echo_off, B, "rbc decode: offsets must not decrease")) return -1;
+    std::vector<uint64_t> eoff, soff(B + 1);
+    if (!rebase(eoff, echo_off, B, "rbc decode: offsets must not decrease")) return -1;
     const int k = n - 2 * f, m = 2 * f, depth = depth_of(n);
-    std::vector<uint64_t> eoff(B + 1), soff(B + 1);
     size_t max_S = 0;
     soff[0] = 0;
-    for (size_t b = 0; b <= B; b++) eoff[b] = echo_off[b] - echo_off[0];
     for (size_t b = 0; b < B; b++) {
         uint64_t bytes = eoff[b + 1] - eoff[b];
         if (bytes % (uint64_t)k) { set_err("rbc decode: an instance's bytes are not n - 2f equal echoes"); return -1; }
@@ -251,21 +237,18 @@ extern "C" int lcb_rbc_decode_batch(uint8_t *shards_out, uint8_t *status, uint8_
             for (int j = 0; j < n; j++) p[j] = j;
         }
     }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
+    HostCall h(c, "rbc decode");
+    hipStream_t s = h.s;
     rs_matrix_lds();
-    const uint8_t *decho = up(c->rbc[0], echo_data + echo_off[0], (size_t)eoff[B], s);
-    const uint64_t *deoff = up(c->rbc[1], eoff.data(), B + 1, s);
-    const uint64_t *dsoff = up(c->rbc[2], soff.data(), B + 1, s);
-    uint8_t *dsh = (uint8_t *)c->rbc[3].get((size_t)soff[B]);
-    const int *dpos = up(c->rbc[4], pos.data(), pos.size(), s);
-    uint8_t *dM = (uint8_t *)c->rbc[5].get(B * (size_t)m * k + B);
-    const uint8_t *dvalid = up(c->rbc[6], valid.data(), B, s);
-    uint8_t *droots = (uint8_t *)c->rbc[7].get(32 * B);
-    if (!decho || !deoff || !dsoff || !dsh || !dpos || !dM || !dvalid || !droots) {
-        set_err("device allocation failed");
-        return -1;
-    }
+    const uint8_t *decho = h.in(echo_data + echo_off[0], (size_t)eoff[B]);
+    const uint64_t *deoff = h.in(eoff.data(), B + 1);
+    const uint64_t *dsoff = h.in(soff.data(), B + 1);
+    uint8_t *dsh = h.out<uint8_t>((size_t)soff[B]);
+    const int *dpos = h.in(pos.data(), pos.size());
+    uint8_t *dM = h.out<uint8_t>(B * (size_t)m * k + B);
+    const uint8_t *dvalid = h.in(valid.data(), B);
+    uint8_t *droots = h.out<uint8_t>(32 * B);
+    if (!h.ok()) return -1;
     uint8_t *dok = dM + B * (size_t)m * k;
     lcbk_rs_matrix_batch(s, dpos, m, k, n, dvalid, dM, dok, (unsigned)B);
     lcbk_rs_apply_batch(s, dM, (size_t)m * k, dok, 1, m, k, n, decho, deoff, dpos, (size_t)n, dsh, dsoff, k, max_S,
@@ -273,10 +256,10 @@ extern "C" int lcb_rbc_decode_batch(uint8_t *shards_out, uint8_t *status, uint8_
     lcbk_rbc_tree(s, dsh, dsoff, n, depth, nullptr, droots, nullptr, (unsigned)B);
     if (!launch_ok("rbc decode launch")) return -1;
     std::vector<uint8_t> roots(32 * B);
-    if (shards_out) hipMemcpyAsync(shards_out, dsh, (size_t)soff[B], hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(status, dok, B, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(roots.data(), droots, 32 * B, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "rbc decode")) return -1;
+    h.back(shards_out, dsh, (size_t)soff[B]);
+    h.back(status, dok, B);
+    h.back(roots.data(), droots, 32 * B);
+    if (h.finish()) return -1;
     for (size_t b = 0; b < B; b++) {
         status[b] = status[b] ? 1 : 0;
         if (!status[b]) memset(&roots[32 * b], 0, 32);
@@ -294,7 +277,7 @@ extern "C" int lcb_ctx_merkle_root_dev(lcb_ctx *ctx, uint8_t *roots_out, uint8_t
     if (n_trees > MAX_ITEMS) { set_err("merkle root: batch too large"); return -1; }
     Enq q(c, (hipStream_t)stream);
     if (!n_trees) return 0;
-    uint8_t *ws = (uint8_t *)c->rbc[8].get(32 * n_hashes);
+    uint8_t *ws = (uint8_t *)c->merkle_ws.get(32 * n_hashes);
     if (!ws) { set_err("device allocation failed"); return -1; }
     lcbk_merkle_root(q.s, roots_out, status, hashes, off, ws, (unsigned)n_trees);
     return launch_ok("merkle root launch") ? 0 : -1;
@@ -309,36 +292,34 @@ extern "C" int lcb_merkle_root_batch(uint8_t *roots_out, uint8_t *status, const 
     if (!c) return -1;
     if (!n_trees) return 0;
     if (n_trees > MAX_ITEMS) { set_err("merkle root: batch too large"); return -1; }
-    if (!monotone(off, n_trees, "merkle root: offsets must not decrease")) return -1;
-    std::vector<uint64_t> rel(n_trees + 1);
-    for (size_t t = 0; t <= n_trees; t++) rel[t] = off[t] - off[0];
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const uint8_t *dh = up(c->rbc[0], hashes + 32 * off[0], 32 * (size_t)rel[n_trees], s);
-    const uint64_t *doff = up(c->rbc[1], rel.data(), n_trees + 1, s);
-    uint8_t *droots = (uint8_t *)c->rbc[7].get(32 * n_trees), *dst = (uint8_t *)c->rbc[9].get(n_trees);
-    if (!dh || !doff || !droots || !dst) { set_err("device allocation failed"); return -1; }
-    if (lcb_ctx_merkle_root_dev(c, droots, dst, dh, doff, n_trees, (size_t)rel[n_trees], s)) return -1;
-    hipMemcpyAsync(roots_out, droots, 32 * n_trees, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(status, dst, n_trees, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "merkle root") ? 0 : -1;
+    std::vector<uint64_t> rel;
+    if (!rebase(rel, off, n_trees, "merkle root: offsets must not decrease")) return -1;
+    HostCall h(c, "merkle root");
+    const uint8_t *dh = h.in(hashes + 32 * off[0], 32 * (size_t)rel[n_trees]);
+    const uint64_t *doff = h.in(rel.data(), n_trees + 1);
+    uint8_t *droots = h.out<uint8_t>(32 * n_trees), *dst = h.out<uint8_t>(n_trees);
+    if (!h.ok()) return -1;
+    if (lcb_ctx_merkle_root_dev(c, droots, dst, dh, doff, n_trees, (size_t)rel[n_trees], h.s)) return -1;
+    h.back(roots_out, droots, 32 * n_trees);
+    h.back(status, dst, n_trees);
+    return h.finish();
 }
 
 // ================================================================== reliable-broadcast Reed-Solomon (k_rs.hip)
 // ReliableBroadcast.ErasureCodingShards / DecodeFromEchos (src/Lachain.Consensus/ReliableBroadcast/ReliableBroadcast.cs:
-// 393-446): the erased / parity shards are M times the known shards, M = H_E^-1 H_K built on the GPU.  Positions and
-// matrix live in the context's dkg[4] / dkg[5] slots, the shards in in[0] / out[0].
+// 393-446): the erased / parity shards are M times the known shards, M = H_E^-1 H_K built on the GPU.  Positions,
+// matrix and shards are staging of the one call.
 namespace {
-int rs_enqueue(lcb_ctx *c, uint8_t *d_out, const uint8_t *d_known, const std::vector<int> &pe,
-               const std::vector<int> &pk, int n, size_t S, hipStream_t s, uint8_t **d_ok) {
+int rs_enqueue(HostCall &h, uint8_t *d_out, const uint8_t *d_known, const std::vector<int> &pe,
+               const std::vector<int> &pk, int n, size_t S, uint8_t **d_ok) {
     rs_matrix_lds();
+    hipStream_t s = h.s;
     int m = (int)pe.size(), k = (int)pk.size();
-    int *dpe = (int *)c->dkg[4].get(4 * (pe.size() + pk.size()));
-    uint8_t *M = (uint8_t *)c->dkg[5].get((size_t)m * k + 16);
-    if (!dpe || !M) { set_err("device allocation failed"); return -1; }
     std::vector<int> both(pe);
     both.insert(both.end(), pk.begin(), pk.end());
-    hipMemcpyAsync(dpe, both.data(), 4 * both.size(), hipMemcpyHostToDevice, s);
+    const int *dpe = h.in(both.data(), both.size());
+    uint8_t *M = h.out<uint8_t>((size_t)m * k + 16);
+    if (!h.ok()) return -1;
     uint8_t *ok = M + (size_t)m * k;
     lcbk_rs_matrix(s, dpe, m, dpe + m, k, n, M, ok);
     lcbk_rs_apply(s, M, ok, m, k, d_known, S, dpe, d_out);
@@ -355,20 +336,20 @@ extern "C" int lcb_rs_encode(uint8_t *shards_out, const uint8_t *input, size_t i
     }
     size_t S = input_len / (size_t)k;
     if (erasures == 0 || S == 0) { memcpy(shards_out, input, input_len); return 0; }
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    uint8_t *dout = (uint8_t *)c->out[0].get(S * n_shards);
-    if (!dout) { set_err("device allocation failed"); return -1; }
+    HostCall h(c, "rs encode");
+    hipStream_t s = h.s;
+    uint8_t *dout = h.out<uint8_t>(S * n_shards);
+    if (!h.ok()) return -1;
     hipMemcpyAsync(dout, input, input_len, hipMemcpyHostToDevice, s);   // data shards stay in place (systematic)
     std::vector<int> pe, pk;
     for (int j = k; j < n_shards; j++) pe.push_back(j);
     for (int j = 0; j < k; j++) pk.push_back(j);
     uint8_t *dok;
-    if (rs_enqueue(c, dout, dout, pe, pk, n_shards, S, s, &dok)) return -1;
+    if (rs_enqueue(h, dout, dout, pe, pk, n_shards, S, &dok)) return -1;
     uint8_t ok = 0;
-    hipMemcpyAsync(shards_out, dout, S * n_shards, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(&ok, dok, 1, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "rs encode")) return -1;
+    h.back(shards_out, dout, S * n_shards);
+    h.back(&ok, dok, 1);
+    if (h.finish()) return -1;
     if (!ok) { set_err("rs encode: parity positions are not independent (more than 255 shards)"); return -1; }
     return 0;
 }
@@ -390,21 +371,21 @@ extern "C" int lcb_rs_decode(uint8_t *out, const uint8_t *echo_data, const int32
     for (int j = 0; j < n_shards; j++) if (!have[j]) pe.push_back(j);
     size_t S = shard_size;
     if (S == 0) return 0;
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    uint8_t *dout = (uint8_t *)c->out[0].get(S * n_shards);
-    const uint8_t *decho = up(c->in[0], echo_data, S * (size_t)n_echos, s);
-    if (!dout || !decho) { set_err("device allocation failed"); return -1; }
+    HostCall h(c, "rs decode");
+    hipStream_t s = h.s;
+    uint8_t *dout = h.out<uint8_t>(S * n_shards);
+    const uint8_t *decho = h.in(echo_data, S * (size_t)n_echos);
+    if (!h.ok()) return -1;
     for (int e = 0; e < n_echos; e++)
         hipMemcpyAsync(dout + (size_t)from[e] * S, decho + (size_t)e * S, S, hipMemcpyDeviceToDevice, s);
     uint8_t ok = 1;
     if (!pe.empty()) {
         uint8_t *dok;
-        if (rs_enqueue(c, dout, decho, pe, pk, n_shards, S, s, &dok)) return -1;
-        hipMemcpyAsync(&ok, dok, 1, hipMemcpyDeviceToHost, s);
+        if (rs_enqueue(h, dout, decho, pe, pk, n_shards, S, &dok)) return -1;
+        h.back(&ok, dok, 1);
     }
-    hipMemcpyAsync(out, dout, S * n_shards, hipMemcpyDeviceToHost, s);
-    if (!sync_check(c, "rs decode")) return -1;
+    h.back(out, dout, S * n_shards);
+    if (h.finish()) return -1;
     if (!ok) { set_err("rs decode: erased positions share an evaluation point (more than 255 shards)"); return -1; }
     return 0;
 }

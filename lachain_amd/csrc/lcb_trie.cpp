@@ -52,7 +52,7 @@ int flat_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *out32, uint8_t *accept, con
     }
     uint32_t *list = nullptr;
     if (!env_on("LCB_TRIE_MIXED")) {                   // measurement switch: one mixed launch
-        list = (uint32_t *)c->trie[0].get(4 * (n + 1));
+        list = (uint32_t *)c->trie[TRIE_LIST].get(4 * (n + 1));
         if (!list) { set_err("device allocation failed"); return -1; }
     }
     lcbk_trie_flat(s, nodes, data, off, expected32, (u32)n, out32, accept, list);
@@ -97,7 +97,7 @@ int root_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *roots32, uint8_t *status, c
         set_err("trie root: the offset arrays must be 8-byte aligned");
         return -1;
     }
-    void *ws = c->trie[1].get(lcbk_trie_root_ws_bytes((u32)n, (u32)B));
+    void *ws = c->trie[TRIE_ROOT_WS].get(lcbk_trie_root_ws_bytes((u32)n, (u32)B));
     if (!ws) { set_err("device allocation failed"); return -1; }
     if (lcbk_trie_roots(s, roots32, status, keys, key_off, values, val_off, trie_off, (u32)B, (u32)n, keys_hashed, ws)) {
         set_err("trie root", hipGetLastError());
@@ -136,22 +136,20 @@ extern "C" int lcb_trie_node_hash_batch(uint8_t *out32, uint8_t *accept, const l
     if (!flat_args_ok(out32, accept, nodes, data, data_off, expected32, n)) return -1;
     if (!n) return 0;
     if (!host_nodes_ok(nodes, data_off, n, "trie node hash")) return -1;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = data_off[i] - data_off[0];
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const lcb_trie_node *dn = up(c->trie[2], nodes, n, s);
-    const uint8_t *dd = up(c->trie[3], data + data_off[0], (size_t)rel[n], s);
-    const uint64_t *doff = up(c->trie[4], rel.data(), n + 1, s);
-    const uint8_t *dexp = accept ? up(c->trie[5], expected32, 32 * n, s) : nullptr;
-    uint8_t *dout = (uint8_t *)c->trie[6].get(33 * n);
-    if (!dn || !dd || !doff || (accept && !dexp) || !dout) { set_err("device allocation failed"); return -1; }
+    std::vector<uint64_t> rel;
+    if (!rebase(rel, data_off, n, "trie node hash: offsets must not decrease")) return -1;
+    HostCall h(c, "trie node hash");
+    const lcb_trie_node *dn = h.in(nodes, n);
+    const uint8_t *dd = h.in(data + data_off[0], (size_t)rel[n]);
+    const uint64_t *doff = h.in(rel.data(), n + 1);
+    const uint8_t *dexp = accept ? h.in(expected32, 32 * n) : nullptr;
+    uint8_t *dout = h.out<uint8_t>(33 * n);
+    if (!h.ok()) return -1;
     uint8_t *dh = out32 ? dout : nullptr, *dacc = accept ? dout + 32 * n : nullptr;
-    if (flat_enqueue(c, s, dh, dacc, (const uint8_t *)dn, dd, doff, dexp, n)) return -1;
-    if (dh) hipMemcpyAsync(out32, dh, 32 * n, hipMemcpyDeviceToHost, s);
-    if (dacc) hipMemcpyAsync(accept, dacc, n, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "trie node hash") ? 0 : -1;
+    if (flat_enqueue(c, h.s, dh, dacc, (const uint8_t *)dn, dd, doff, dexp, n)) return -1;
+    h.back(out32, dh, 32 * n);
+    h.back(accept, dacc, n);
+    return h.finish();
 }
 
 // ------------------------------------------------------------------ (b) rehash by reference
@@ -194,8 +192,10 @@ extern "C" int lcb_trie_rehash_batch(uint8_t *hash_out32, const lcb_trie_node *n
         return -1;
     }
     if (!host_nodes_ok(nodes, data_off, n, what)) return -1;
-    for (size_t i = 0; i < n; i++)
-        if (child_off[i + 1] < child_off[i]) { fail(what, "child offsets must not decrease"); return -1; }
+    std::vector<uint64_t> rel, crel;
+    if (!rebase(rel, data_off, n, "trie rehash: offsets must not decrease") ||
+        !rebase(crel, child_off, n, "trie rehash: child offsets must not decrease"))
+        return -1;
     const uint64_t base = child_off[0], n_refs = child_off[n] - base;
     if (n_refs && !child_ref) { fail(what, "child_ref is required"); return -1; }
     // heights: a node without in-batch children has height 0, a parent one more than its highest in-batch child.
@@ -240,23 +240,19 @@ extern "C" int lcb_trie_rehash_batch(uint8_t *hash_out32, const lcb_trie_node *n
         std::vector<uint64_t> at(level_off.begin(), level_off.end() - 1);
         for (size_t i = 0; i < n; i++) by_level[at[height[i]]++] = i;
     }
-    std::vector<uint64_t> rel(n + 1), crel(n + 1);
-    for (size_t i = 0; i <= n; i++) { rel[i] = data_off[i] - data_off[0]; crel[i] = child_off[i] - base; }
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const lcb_trie_node *dn = up(c->trie[2], nodes, n, s);
-    const uint8_t *dd = up(c->trie[3], data + data_off[0], (size_t)rel[n], s);
-    const uint64_t *doff = up(c->trie[4], rel.data(), n + 1, s);
-    const uint8_t *dlit = up(c->trie[5], literals32, 32 * n_literals, s);
-    uint8_t *dout = (uint8_t *)c->trie[6].get(32 * n);
-    const uint64_t *dcoff = up(c->trie[7], crel.data(), n + 1, s);
-    const int64_t *dref = up(c->trie[8], n_refs ? child_ref + base : nullptr, (size_t)n_refs, s);
-    const uint64_t *dord = up(c->trie[9], by_level.data(), n, s);
-    if (!dn || !dd || !doff || !dlit || !dout || !dcoff || !dref || !dord) { set_err("device allocation failed"); return -1; }
-    if (rehash_enqueue(c, s, dout, (const uint8_t *)dn, dd, doff, dcoff, dref, dlit, dord, level_off.data(), max_h + 1)) return -1;
-    hipMemcpyAsync(hash_out32, dout, 32 * n, hipMemcpyDeviceToHost, s);
-    return sync_check(c, what) ? 0 : -1;
+    HostCall h(c, what);
+    const lcb_trie_node *dn = h.in(nodes, n);
+    const uint8_t *dd = h.in(data + data_off[0], (size_t)rel[n]);
+    const uint64_t *doff = h.in(rel.data(), n + 1);
+    const uint8_t *dlit = h.in(literals32, 32 * n_literals);
+    uint8_t *dout = h.out<uint8_t>(32 * n);
+    const uint64_t *dcoff = h.in(crel.data(), n + 1);
+    const int64_t *dref = h.in(n_refs ? child_ref + base : nullptr, (size_t)n_refs);
+    const uint64_t *dord = h.in(by_level.data(), n);
+    if (!h.ok()) return -1;
+    if (rehash_enqueue(c, h.s, dout, (const uint8_t *)dn, dd, doff, dcoff, dref, dlit, dord, level_off.data(), max_h + 1)) return -1;
+    h.back(hash_out32, dout, 32 * n);
+    return h.finish();
 }
 
 // ------------------------------------------------------------------ (c) roots from key/value sets
@@ -297,20 +293,20 @@ extern "C" int lcb_trie_root_batch(uint8_t *roots32, uint8_t *status, const uint
         }
         if (keys_hashed && key_off[i + 1] - key_off[i] != 32) { fail(what, "a key hash is 32 bytes"); return -1; }
     }
-    std::vector<uint64_t> krel(n + 1, 0), vrel(n + 1, 0);
-    for (size_t i = 0; n && i <= n; i++) { krel[i] = key_off[i] - key_off[0]; vrel[i] = val_off[i] - val_off[0]; }
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const uint8_t *dk = up(c->trie[2], n ? keys + key_off[0] : keys, (size_t)krel[n], s);
-    const uint8_t *dv = up(c->trie[3], n ? values + val_off[0] : values, (size_t)vrel[n], s);
-    const uint64_t *dko = up(c->trie[4], krel.data(), n + 1, s);
-    const uint64_t *dvo = up(c->trie[5], vrel.data(), n + 1, s);
-    uint8_t *dout = (uint8_t *)c->trie[6].get(33 * B);
-    const uint64_t *dto = up(c->trie[7], trie_off, B + 1, s);
-    if (!dk || !dv || !dko || !dvo || !dout || !dto) { set_err("device allocation failed"); return -1; }
-    if (root_enqueue(c, s, dout, dout + 32 * B, dk, dko, dv, dvo, dto, B, n, keys_hashed)) return -1;
-    hipMemcpyAsync(roots32, dout, 32 * B, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(status, dout + 32 * B, B, hipMemcpyDeviceToHost, s);
-    return sync_check(c, what) ? 0 : -1;
+    std::vector<uint64_t> krel, vrel;
+    if (!rebase(krel, key_off, n, "trie root: offsets must not decrease") ||
+        !rebase(vrel, val_off, n, "trie root: offsets must not decrease"))
+        return -1;
+    HostCall h(c, what);
+    const uint8_t *dk = h.in(n ? keys + key_off[0] : keys, (size_t)krel[n]);
+    const uint8_t *dv = h.in(n ? values + val_off[0] : values, (size_t)vrel[n]);
+    const uint64_t *dko = h.in(krel.data(), n + 1);
+    const uint64_t *dvo = h.in(vrel.data(), n + 1);
+    uint8_t *dout = h.out<uint8_t>(33 * B);
+    const uint64_t *dto = h.in(trie_off, B + 1);
+    if (!h.ok()) return -1;
+    if (root_enqueue(c, h.s, dout, dout + 32 * B, dk, dko, dv, dvo, dto, B, n, keys_hashed)) return -1;
+    h.back(roots32, dout, 32 * B);
+    h.back(status, dout + 32 * B, B);
+    return h.finish();
 }

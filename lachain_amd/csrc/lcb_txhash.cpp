@@ -66,7 +66,7 @@ int hash_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *raw32, uint8_t *full32, uin
                  size_t n, int32_t chain_id, bool last_phase) {
     if (((uintptr_t)txs | (uintptr_t)off) & 7) { set_err("tx hash: txs and inv_off must be 8-byte aligned"); return -1; }
     if (!events_ready(c)) return -1;
-    uint32_t *long_ws = (uint32_t *)c->tx[12].get(4 * (n + 1));    // k_tx_hash's list of long items
+    uint32_t *long_ws = (uint32_t *)c->tx[TX_LONG].get(4 * (n + 1));    // k_tx_hash's list of long items
     if (!long_ws) { set_err("device allocation failed"); return -1; }
     (void)hipEventRecord(c->tx_ev[0], s);
     lcbk_tx_hash(s, txs, inv, off, sigs, (u32)sig_len, claimed, (u32)chain_id, (u32)n, raw32, full32, match, long_ws);
@@ -85,8 +85,8 @@ int receipts_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *accept, uint8_t *detail
                      size_t n, const uint64_t *tx_off, const uint8_t *expected_roots, size_t n_blocks,
                      int use_new_chain_id, int32_t chain_id) {
     if (n) {
-        uint8_t *raw = (uint8_t *)c->tx[0].get(32 * n), *flags = (uint8_t *)c->tx[1].get(2 * n);
-        uint8_t *addr = (uint8_t *)c->tx[2].get(20 * n);
+        uint8_t *raw = (uint8_t *)c->tx[TX_RAW].get(32 * n), *flags = (uint8_t *)c->tx[TX_FLAGS].get(2 * n);
+        uint8_t *addr = (uint8_t *)c->tx[TX_ADDR].get(20 * n);
         if (!raw || !flags || !addr) { set_err("device allocation failed"); return -1; }
         uint8_t *match = flags, *rec_ok = flags + n;
         if (hash_enqueue(c, s, raw, nullptr, match, txs, inv, off, sigs, sig_len, claimed, n, chain_id, false)) return -1;
@@ -101,7 +101,7 @@ int receipts_enqueue(lcb_ctx *c, hipStream_t s, uint8_t *accept, uint8_t *detail
     }
     (void)hipEventRecord(c->tx_ev[2], s);
     if (n_blocks) {
-        uint8_t *roots = (uint8_t *)c->tx[3].get(33 * n_blocks);
+        uint8_t *roots = (uint8_t *)c->tx[TX_ROOTS].get(33 * n_blocks);
         if (!roots) { set_err("device allocation failed"); return -1; }
         if (lcb_ctx_merkle_root_dev(c, roots, roots + 32 * n_blocks, claimed, tx_off, n_blocks, n, s)) return -1;
         lcbk_tx_root_ok(s, roots, expected_roots, (u32)n_blocks, root_ok);
@@ -152,31 +152,26 @@ int receipts_host(uint8_t *accept, uint8_t *detail, uint8_t *root_ok, const lcb_
         }
     }
     if (!n && !n_blocks) return 0;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = n ? off[i] - off[0] : 0;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const lcb_tx_fields *dtx = up(c->tx[4], txs, n, s);
-    const uint8_t *dinv = up(c->tx[5], n ? inv + off[0] : inv, (size_t)rel[n], s);
-    const uint64_t *doff = up(c->tx[6], rel.data(), n + 1, s);
-    const uint8_t *dsig = up(c->tx[7], sigs, sig_len * n, s);
-    const uint8_t *dclaim = up(c->tx[8], claimed, 32 * n, s);
-    uint8_t *dout = (uint8_t *)c->tx[9].get(2 * n + n_blocks);
-    const uint64_t *dtoff = n_blocks ? up(c->tx[10], tx_off, n_blocks + 1, s) : nullptr;
-    const uint8_t *dexp = n_blocks ? up(c->tx[11], expected_roots, 32 * n_blocks, s) : nullptr;
-    if (!dtx || !dinv || !doff || !dsig || !dclaim || !dout || (n_blocks && (!dtoff || !dexp))) {
-        set_err("device allocation failed");
-        return -1;
-    }
+    std::vector<uint64_t> rel;
+    if (!rebase(rel, off, n, "receipts verify: offsets must not decrease")) return -1;
+    HostCall h(c, what);
+    const lcb_tx_fields *dtx = h.in(txs, n);
+    const uint8_t *dinv = h.in(n ? inv + off[0] : inv, (size_t)rel[n]);
+    const uint64_t *doff = h.in(rel.data(), n + 1);
+    const uint8_t *dsig = h.in(sigs, sig_len * n);
+    const uint8_t *dclaim = h.in(claimed, 32 * n);
+    uint8_t *dout = h.out<uint8_t>(2 * n + n_blocks);
+    const uint64_t *dtoff = n_blocks ? h.in(tx_off, n_blocks + 1) : nullptr;
+    const uint8_t *dexp = n_blocks ? h.in(expected_roots, 32 * n_blocks) : nullptr;
+    if (!h.ok()) return -1;
     uint8_t *dacc = dout, *ddet = dout + n, *drok = dout + 2 * n;
-    if (receipts_enqueue(c, s, dacc, ddet, drok, (const uint8_t *)dtx, dinv, doff, dsig, sig_len, dclaim, n, dtoff, dexp,
+    if (receipts_enqueue(c, h.s, dacc, ddet, drok, (const uint8_t *)dtx, dinv, doff, dsig, sig_len, dclaim, n, dtoff, dexp,
                          n_blocks, use_new_chain_id, chain_id))
         return -1;
-    if (n) hipMemcpyAsync(accept, dacc, n, hipMemcpyDeviceToHost, s);
-    if (n && detail) hipMemcpyAsync(detail, ddet, n, hipMemcpyDeviceToHost, s);
-    if (n_blocks) hipMemcpyAsync(root_ok, drok, n_blocks, hipMemcpyDeviceToHost, s);
-    return sync_check(c, what) ? 0 : -1;
+    h.back(accept, dacc, n);
+    h.back(detail, ddet, n);
+    h.back(root_ok, drok, n_blocks);
+    return h.finish();
 }
 
 }  // namespace
@@ -215,23 +210,21 @@ extern "C" int lcb_tx_hash_batch(uint8_t *raw32_out, uint8_t *full32_out, const 
     if (!common_ok(n, txs, invocations, inv_off, sig_len, sigs != nullptr, use_new_chain_id, chain_id, "tx hash")) return -1;
     if (!n) return 0;
     if (!host_items_ok(txs, inv_off, n, "tx hash")) return -1;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = inv_off[i] - inv_off[0];
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    Enq q(c, c->stream);
-    hipStream_t s = c->stream;
-    const lcb_tx_fields *dtx = up(c->tx[4], txs, n, s);
-    const uint8_t *dinv = up(c->tx[5], invocations + inv_off[0], (size_t)rel[n], s);
-    const uint64_t *doff = up(c->tx[6], rel.data(), n + 1, s);
-    const uint8_t *dsig = sigs ? up(c->tx[7], sigs, sig_len * n, s) : nullptr;
-    uint8_t *dout = (uint8_t *)c->tx[9].get(64 * n);
-    if (!dtx || !dinv || !doff || (sigs && !dsig) || !dout) { set_err("device allocation failed"); return -1; }
+    std::vector<uint64_t> rel;
+    if (!rebase(rel, inv_off, n, "tx hash: offsets must not decrease")) return -1;
+    HostCall h(c, "tx hash");
+    const lcb_tx_fields *dtx = h.in(txs, n);
+    const uint8_t *dinv = h.in(invocations + inv_off[0], (size_t)rel[n]);
+    const uint64_t *doff = h.in(rel.data(), n + 1);
+    const uint8_t *dsig = sigs ? h.in(sigs, sig_len * n) : nullptr;
+    uint8_t *dout = h.out<uint8_t>(64 * n);
+    if (!h.ok()) return -1;
     uint8_t *draw = raw32_out ? dout : nullptr, *dfull = sigs && full32_out ? dout + 32 * n : nullptr;
-    if (hash_enqueue(c, s, draw, dfull, nullptr, (const uint8_t *)dtx, dinv, doff, dsig, sig_len, nullptr, n, chain_id, true))
+    if (hash_enqueue(c, h.s, draw, dfull, nullptr, (const uint8_t *)dtx, dinv, doff, dsig, sig_len, nullptr, n, chain_id, true))
         return -1;
-    if (draw) hipMemcpyAsync(raw32_out, draw, 32 * n, hipMemcpyDeviceToHost, s);
-    if (dfull) hipMemcpyAsync(full32_out, dfull, 32 * n, hipMemcpyDeviceToHost, s);
-    return sync_check(c, "tx hash") ? 0 : -1;
+    h.back(raw32_out, draw, 32 * n);
+    h.back(full32_out, dfull, 32 * n);
+    return h.finish();
 }
 
 // ------------------------------------------------------------------ VerifyTransactionImmediately
