@@ -209,7 +209,8 @@ int lcb_tpke_partial_decrypt(uint8_t *ui_out, uint8_t *status, const uint8_t x[3
 
 /* TPKE.PublicKey.Encrypt for a batch with caller-supplied randomness r (TPKE/PublicKey.cs:25-37):
    U = rG, T = rY (serialized, for the XorWithHash KDF done by the caller), W = r H(U||V). Two-phase
-   because V = data XOR KDF(T) is computed between the phases (TPKE/Utils.cs:12-19). */
+   because V = data XOR KDF(T) is computed between the phases (TPKE/Utils.cs:12-19).  lcb_tpke_encrypt_batch
+   ("TPKE keystream on the device" below) is the whole of Encrypt in one call. */
 int lcb_tpke_encrypt_phase1(uint8_t *u_out, uint8_t *t_out, const uint8_t y[48], const uint8_t *r, size_t n);
 int lcb_tpke_encrypt_phase2(uint8_t *w_out, const uint8_t *u, const uint8_t *r, const uint8_t *v_data,
                             const uint32_t *v_off, size_t n);
@@ -248,7 +249,8 @@ int lcb_tpke_partial_decrypt_prepared_dev(uint8_t *ui_out, uint8_t *status, cons
 /* TPKE.PublicKey.FullDecrypt's combination step (TPKE/PublicKey.cs:74-84) for whole batches: ciphertext c owns
    shares [c*per_ct, (c+1)*per_ct) ordered by DecryptorId, with verification bits in accept; the first k
    accepted shares (x = DecryptorId + 1) are Lagrange-combined in G1: u_out[c] = sum lambda_i U_i (48 B),
-   status[c] = 0 with fewer than k valid shares.  The plaintext is then lcb_xor_with_hash(u, V) on the host. */
+   status[c] = 0 with fewer than k valid shares.  The plaintext is then lcb_xor_with_hash(u, V) on the host
+   (lcb_tpke_full_decrypt_dev, "TPKE keystream on the device" below, goes on to the plaintext on the device). */
 int lcb_tpke_combine_dev(uint8_t *u_out, uint8_t *status, const uint8_t *accept, const uint8_t *shares,
                          size_t per_ct, size_t k, size_t n_cts, void *stream);
 /* Arrival-order forms of the two combinations: HoneyBadger.cs:237-247 / ThresholdSigner.cs:62-75 combine the first
@@ -1014,6 +1016,56 @@ int lcb_g2_hash_batch(uint8_t *out, const uint8_t *msg_data, const uint32_t *msg
 /* TPKE Utils.XorWithHash (BouncyCastle DigestRandomGenerator(Sha3Digest) keystream, TPKE/Utils.cs:12-19):
    host-side byte work, provided so a non-.NET host can finish FullDecrypt/Encrypt. */
 void lcb_xor_with_hash(uint8_t *out, const uint8_t g1[48], const uint8_t *data, size_t len);
+
+/* ------------------------------------------------------------------ TPKE keystream on the device (k_kdf.hip)
+   Utils.XorWithHash for batches, and with it PublicKey.Encrypt and PublicKey.FullDecrypt in one call each: the
+   keystream runs between (Encrypt) or behind (FullDecrypt) the kernels of lcb_tpke_encrypt_phase1 / _phase2 and
+   lcb_tpke_combine_dev on one stream, and T = rY and u = sum lambda_i U_i never leave the device.  One item per lane:
+   the generator's chain is sequential within an item (one Keccak permutation per 32 bytes), so these calls are for
+   batches; a single item is faster through lcb_xor_with_hash.
+   Items are packed as in the TPKE calls' v_data / v_off: item i is the bytes [off[i], off[i + 1]) of its array, with
+   n + 1 non-decreasing uint32 offsets; every output is packed as its input, i.e. out item i lies at out + data_off[i].
+   Items may start at any byte alignment.  out == data (in place) is allowed; any other overlap of an output with an
+   input is not supported.  The *_dev forms take device pointers, are asynchronous on `stream`, trust their offsets and
+   synchronise nothing; the host-pointer forms fail the call on a decreasing offset pair.  n = 0 is a successful no-op.
+   T, u and r open the ciphertext: the device buffers of T and u and a host form's staged copy of r are cleared on the
+   stream before the call returns.  No constant-time claim is made (the standing of the ECIES calls above). */
+/* out item i = data item i ^ DigestRandomGenerator(Sha3Digest) seeded with seeds[seed_off[i] .. seed_off[i + 1]); a seed
+   of any length, zero included (TPKE/Utils.cs:12-19 with a 48-byte G1 seed) */
+int lcb_xor_with_hash_batch(uint8_t *out, const uint8_t *seeds, const uint32_t *seed_off, const uint8_t *data,
+                            const uint32_t *data_off, size_t n);
+int lcb_ctx_xor_with_hash_dev(lcb_ctx *ctx, uint8_t *out, const uint8_t *seeds, const uint32_t *seed_off,
+                              const uint8_t *data, const uint32_t *data_off, size_t n, void *stream);
+int lcb_xor_with_hash_dev(uint8_t *out, const uint8_t *seeds, const uint32_t *seed_off, const uint8_t *data,
+                          const uint32_t *data_off, size_t n, void *stream);
+/* PublicKey.Encrypt for a batch with caller-supplied randomness r (TPKE/PublicKey.cs:25-37): U = rG (48 B per item),
+   V = data ^ KDF(rY) (packed as data), W = r H(U || V) (96 B per item).  The host form fails where the two phases fail:
+   "invalid public key or scalar" (y malformed, r >= the group order), "hash-to-G2 failed".  The *_dev form reports
+   those per item: ok[i] = 0 (nullable), V item i zero bytes when the key or scalar is invalid. */
+int lcb_tpke_encrypt_batch(uint8_t *u_out, uint8_t *v_out, uint8_t *w_out, const uint8_t y[48], const uint8_t *r,
+                           const uint8_t *data, const uint32_t *data_off, size_t n);
+int lcb_ctx_tpke_encrypt_dev(lcb_ctx *ctx, uint8_t *u_out, uint8_t *v_out, uint8_t *w_out, uint8_t *ok, const uint8_t *y,
+                             const uint8_t *r, const uint8_t *data, const uint32_t *data_off, size_t n, void *stream);
+int lcb_tpke_encrypt_dev(uint8_t *u_out, uint8_t *v_out, uint8_t *w_out, uint8_t *ok, const uint8_t *y, const uint8_t *r,
+                         const uint8_t *data, const uint32_t *data_off, size_t n, void *stream);
+/* PublicKey.FullDecrypt behind lcb_tpke_combine_dev / lcb_tpke_combine_ordered_dev: the same grouped arguments (order
+   null: index order) plus the ciphertexts' V; pt_out item c = V_c ^ KDF(u_c), packed as v_data, zero bytes where
+   status[c] = 0 (fewer than k accepted shares, a repeated position). */
+int lcb_ctx_tpke_full_decrypt_dev(lcb_ctx *ctx, uint8_t *pt_out, uint8_t *status, const uint8_t *accept,
+                                  const uint8_t *shares, const uint32_t *order, size_t per_ct, size_t k,
+                                  const uint8_t *v_data, const uint32_t *v_off, size_t n_cts, void *stream);
+int lcb_tpke_full_decrypt_dev(uint8_t *pt_out, uint8_t *status, const uint8_t *accept, const uint8_t *shares,
+                              const uint32_t *order, size_t per_ct, size_t k, const uint8_t *v_data,
+                              const uint32_t *v_off, size_t n_cts, void *stream);
+/* PublicKey.FullDecrypt literally (TPKE/PublicKey.cs:74-84) for a batch: problem j combines ALL its entries
+   off[j] .. off[j + 1) (share uis[e] at x = ids[e] + 1) and opens V_j; status as lcb_g1_lagrange_batch (0 for a repeated
+   id), pt_out item j zero bytes where status[j] = 0.  The count and share-id checks are the caller's. */
+int lcb_tpke_full_decrypt_batch(uint8_t *pt_out, uint8_t *status, const int32_t *ids, const uint8_t *uis,
+                                const uint32_t *off, const uint8_t *v_data, const uint32_t *v_off, size_t n_cts);
+/* kernel milliseconds of k_kdf_xor in the last keystream call (any of the above) of the context (null: the calling
+   thread's *_dev context) / of the calling thread's host-pointer forms; waits for that call */
+int lcb_ctx_kdf_phase_ms(lcb_ctx *ctx, float ms[1]);
+int lcb_kdf_phase_ms(float ms[1]);
 
 #ifdef __cplusplus
 }

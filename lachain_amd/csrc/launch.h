@@ -116,6 +116,10 @@ extern "C" void lcbk_trie_flat(hipStream_t s, const uint8_t *nodes, const uint8_
 extern "C" void lcbk_trie_level(hipStream_t s, uint8_t *hashes32, const uint8_t *nodes, const uint8_t *data, const uint64_t *off, const uint64_t *child_off, const int64_t *child_ref, const uint8_t *literals32, const uint64_t *order, u32 count);
 extern "C" size_t lcbk_trie_root_ws_bytes(u32 n, u32 B);
 extern "C" int lcbk_trie_roots(hipStream_t s, uint8_t *roots32, uint8_t *status, const uint8_t *keys, const uint64_t *key_off, const uint8_t *values, const uint64_t *val_off, const uint64_t *trie_off, u32 B, u32 n, int keys_hashed, void *ws);
+// the TPKE keystream (k_kdf.hip): out = data ^ DigestRandomGenerator(seed material), one item per lane; ok nullable
+extern "C" void lcbk_kdf_xor(hipStream_t s, uint8_t *out, const uint8_t *seeds, const uint32_t *seed_off, const uint8_t *data, const uint32_t *data_off, const uint8_t *ok, u32 n);
+extern "C" void lcbk_kdf_xor_strided(hipStream_t s, uint8_t *out, const uint8_t *seeds, u32 seed_stride, const uint8_t *data, const uint32_t *data_off, const uint8_t *ok, u32 n);
+extern "C" void lcbk_tpke_ids_to_x(hipStream_t s, const int32_t *ids, u32 ne, uint8_t *xs);
 extern "C" size_t lcbk_ecdh_job_bytes(void);
 extern "C" size_t lcbk_ecdh_point_bytes(void);
 extern "C" void lcbk_ecdh_scalars(hipStream_t s, const uint8_t *pub, const uint64_t *off, u32 min_len, const uint8_t *scalars32, const u32 *idx, u32 n_scalars, u32 n, void *jobs);

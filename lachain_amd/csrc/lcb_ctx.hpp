@@ -181,8 +181,17 @@ enum TrieBuf {        // lcb_ctx::trie, the state trie
     TRIE_ROOT_WS,     // the root builder's workspace (lcbk_trie_root_ws_bytes); root_enqueue
     TRIE_N
 };
+enum KdfBuf {         // lcb_ctx::kdf, the TPKE keystream and its compositions (n items; ne entries of the literal form)
+    KDF_T,            // Encrypt: T = r Y per item, the keystream's seeds, 48 n B, cleared after use; encrypt_enqueue
+    KDF_OK1,          // Encrypt: the first phase's validity when the caller passes no ok, n B; lcb_ctx_tpke_encrypt_dev
+    KDF_OK2,          // Encrypt: the second phase's validity, merged into the caller's ok, n B; the same
+    KDF_U,            // FullDecrypt: u = sum lambda_i U_i per ciphertext, the seeds, 48 n B, cleared after use;
+                      // lcb_ctx_tpke_full_decrypt_dev / literal_enqueue
+    KDF_XS,           // FullDecrypt, literal form: the evaluation points ids + 1 as Fr values, 32 ne B; literal_enqueue
+    KDF_N
+};
 struct lcb_ctx {
-    std::recursive_mutex mu;        // one enqueue at a time per context (contexts may be shared by threads)
+    std::recursive_mutex mu;      // one enqueue at a time per context (contexts may be shared by threads)
     int device = 0;
     hipStream_t stream = nullptr;   // for the synchronous host-pointer entry points
     hipEvent_t order = nullptr;     // completion of the last work enqueued in this context
@@ -288,6 +297,10 @@ struct lcb_ctx {
     bool tx_ev_ready = false, tx_ran = false;
     // state trie (lcb_trie.cpp)
     DevBuf trie[TRIE_N];
+    // TPKE keystream and the one-call Encrypt / FullDecrypt (lcb_kdf.cpp)
+    DevBuf kdf[KDF_N];
+    hipEvent_t kdf_ev[2] = {};        // around k_kdf_xor of the last call
+    bool kdf_ev_ready = false, kdf_ran = false;
 };
 
 // Enqueue scope: exclusive use of the context, stream ordered after the context's previous work, and the

@@ -6,7 +6,8 @@
 // Elsewhere: the mcl single-element surface (lcb_mcl.cpp), the randomized batch check behind the *_batched entry
 // points (lcb_batch.cpp; the exact checks and the preparations both use are here), the trustless-DKG commitments
 // (lcb_dkg.cpp), Reed-Solomon and the reliable-broadcast Merkle layer (lcb_rbc.cpp), secp256k1 ECDSA / ECIES
-// (lcb_ecdsa.cpp, lcb_ecies.cpp) and transaction hashing (lcb_txhash.cpp).  What they share is in lcb_internal.hpp.
+// (lcb_ecdsa.cpp, lcb_ecies.cpp), transaction hashing (lcb_txhash.cpp) and the device keystream with the one-call
+// TPKE Encrypt / FullDecrypt (lcb_kdf.cpp).  What they share is in lcb_internal.hpp.
 // There is deliberately no CPU fallback for the GPU work: without a gfx950 device mclBn_init returns -1 and every
 // entry point fails (returns -1 / 0 bytes / leaves outputs zeroed) with lcb_last_error() describing why.
 //
@@ -393,6 +394,7 @@ void ctx_free(lcb_ctx *c) {
     lcb_int::ecies_ctx_release(c);
     lcb_int::txhash_ctx_release(c);
     lcb_int::trie_ctx_release(c);
+    lcb_int::kdf_ctx_release(c);
     if (c->ver_ev_ready) for (auto &e : c->ver_ev) (void)hipEventDestroy(e);
     if (c->msm_ev_ready) for (auto &e : c->msm_ev) (void)hipEventDestroy(e);
     if (c->order) (void)hipEventDestroy(c->order);
@@ -637,9 +639,8 @@ int lcb_int::lagrange_enqueue(lcb_ctx *c, int g, uint8_t *dout, uint8_t *dst, co
     else lcbk_g2_sum(dim3(nblk(np)), s, parts, pok, doff, (u32)np, dst, dout);
     return launch_ok("lagrange launch") ? 0 : -1;
 }
-namespace {
-int assemble_enqueue(lcb_ctx *c, int g, uint8_t *out, uint8_t *status, const uint8_t *accept, const uint8_t *pts,
-                     size_t per_group, size_t k, size_t n_groups, hipStream_t s, const uint32_t *order = nullptr) {
+int lcb_int::assemble_enqueue(lcb_ctx *c, int g, uint8_t *out, uint8_t *status, const uint8_t *accept, const uint8_t *pts,
+                              size_t per_group, size_t k, size_t n_groups, hipStream_t s, const uint32_t *order) {
     if (!n_groups) return 0;
     if (k == 0 || k > per_group) { set_err("assemble: need 0 < k <= shares per group"); return -1; }
     size_t pb = g == 1 ? 48 : 96, ne = n_groups * k;
@@ -653,6 +654,7 @@ int assemble_enqueue(lcb_ctx *c, int g, uint8_t *out, uint8_t *status, const uin
                             ys, off, order, src);
     return lagrange_enqueue(c, g, out, status, xs, ys, off, n_groups, ne, s, src, g == 2 && k % 2 == 0);
 }
+namespace {
 
 // ------------------------------------------------------------------ Pippenger MSM (k_msm.hip)
 // window width minimising ceil-windows * (n mixed adds * 11 + 2^(c-1) buckets * 2 Jacobian adds * 16) Fp-mul

@@ -34,6 +34,7 @@ void ecdsa_ctx_release(lcb_ctx *c);   // lcb_ecdsa.cpp: the context's cached key
 void ecies_ctx_release(lcb_ctx *c);   // lcb_ecies.cpp: the envelope workspaces and events
 void txhash_ctx_release(lcb_ctx *c);  // lcb_txhash.cpp: the transaction workspaces and events
 void trie_ctx_release(lcb_ctx *c);    // lcb_trie.cpp: the state-trie workspaces
+void kdf_ctx_release(lcb_ctx *c);     // lcb_kdf.cpp: the keystream compositions' workspaces and events
 
 // ---- lcb_host.cpp, for lcb_batch.cpp
 bool env_on(const char *name);              // an opt-in switch of the environment, read at call time
@@ -49,6 +50,10 @@ bool ts_shape_ok(lcb_ctx *c, size_t n_pks, size_t n_msgs, const char *what);
 int lagrange_enqueue(lcb_ctx *c, int g, uint8_t *dout, uint8_t *dst, const uint8_t *dx, const uint8_t *dy,
                      const uint32_t *doff, size_t np, size_t ne, hipStream_t s, const uint32_t *src = nullptr,
                      bool pairs = false);
+
+// ---- lcb_host.cpp, for lcb_kdf.cpp: the first k accepted shares of every group (index order, or `order`), combined at 0
+int assemble_enqueue(lcb_ctx *c, int g, uint8_t *out, uint8_t *status, const uint8_t *accept, const uint8_t *pts,
+                     size_t per_group, size_t k, size_t n_groups, hipStream_t s, const uint32_t *order = nullptr);
 
 // ---- lcb_batch.cpp, for lcb_host.cpp
 extern std::atomic<uint32_t> g_coop_max;    // lcb_set_coop_max: the exact TPKE check (tpke_verify_core) reads it too

@@ -274,6 +274,15 @@ _SIGS = {
     "lcb_trie_rehash_dev": (ctypes.c_int, [ctypes.c_void_p] * 8 + [c_u64p, c_size, c_size, ctypes.c_void_p]),
     "lcb_trie_root_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u64p, c_u8p, c_u64p, c_u64p, c_size, ctypes.c_int]),
     "lcb_trie_root_dev": (ctypes.c_int, [ctypes.c_void_p] * 7 + [c_size, c_size, ctypes.c_int, ctypes.c_void_p]),
+    "lcb_xor_with_hash_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u32p, c_u8p, c_u32p, c_size]),
+    "lcb_xor_with_hash_dev": (ctypes.c_int, [ctypes.c_void_p] * 5 + [c_size, ctypes.c_void_p]),
+    "lcb_tpke_encrypt_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u32p, c_size]),
+    "lcb_tpke_encrypt_dev": (ctypes.c_int, [ctypes.c_void_p] * 8 + [c_size, ctypes.c_void_p]),
+    "lcb_tpke_full_decrypt_dev": (ctypes.c_int, [ctypes.c_void_p] * 5 + [c_size, c_size, ctypes.c_void_p,
+                                                                        ctypes.c_void_p, c_size, ctypes.c_void_p]),
+    "lcb_tpke_full_decrypt_batch": (ctypes.c_int, [c_u8p, c_u8p, ctypes.POINTER(ctypes.c_int32), c_u8p, c_u32p, c_u8p,
+                                                   c_u32p, c_size]),
+    "lcb_kdf_phase_ms": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float)]),
     "lcb_ctx_create": (ctypes.c_void_p, []),
     "lcb_ctx_destroy": (None, [ctypes.c_void_p]),
     "lcb_ctx_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
@@ -289,7 +298,7 @@ for _name in ("tpke_prepare_dev", "tpke_verify_prepared_dev", "tpke_verify_prepa
               "rbc_check_echo_dev", "rbc_merkle_tree_dev", "merkle_root_dev", "secp_ecdh_dev", "aes256_gcm_encrypt_dev",
               "aes256_gcm_decrypt_dev", "secp256k1_encrypt_dev", "secp256k1_decrypt_dev", "ecies_phase_ms", "tx_hash_dev",
               "receipts_verify_dev", "block_txs_verify_dev", "tx_phase_ms", "trie_node_hash_dev", "trie_rehash_dev",
-              "trie_root_dev"):
+              "trie_root_dev", "xor_with_hash_dev", "tpke_encrypt_dev", "tpke_full_decrypt_dev", "kdf_phase_ms"):
     _res, _args = _SIGS["lcb_" + _name]
     _SIGS["lcb_ctx_" + _name] = (_res, [ctypes.c_void_p] + list(_args))
 
@@ -553,6 +562,74 @@ def _i32_keep(keep, vals):
     arr = (ctypes.c_int32 * max(1, len(vals)))(*vals)
     keep.append(arr)
     return ctypes.cast(arr, ctypes.POINTER(ctypes.c_int32))
+
+
+def _split(raw, off):
+    return [raw[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+
+def xor_with_hash_batch(seeds, datas):
+    """Utils.XorWithHash on the device (lcb_xor_with_hash_batch): datas[i] ^ the keystream seeded with seeds[i] (any
+    length; the TPKE paths' seed is a serialised G1 point).  Returns the list of outputs."""
+    keep = []
+    n = len(datas)
+    assert len(seeds) == n
+    soff, doff = _offsets(seeds), _offsets(datas)
+    _, ps = _bytes_ptr_keep(keep, b"".join(seeds))
+    _, pso = _u32_keep(keep, soff)
+    _, pd = _bytes_ptr_keep(keep, b"".join(datas))
+    _, pdo = _u32_keep(keep, doff)
+    ob, po = _out(doff[-1])
+    _check(lib().lcb_xor_with_hash_batch(po, ps, pso, pd, pdo, n), "xor_with_hash_batch")
+    return _split(bytes(ob), doff)
+
+
+def tpke_encrypt_batch(y48, rs, datas):
+    """PublicKey.Encrypt for a batch in one call (lcb_tpke_encrypt_batch): rs[i] the 32-byte scalar, datas[i] the
+    payload.  Returns [(U48, V, W96)]."""
+    keep = []
+    n = len(datas)
+    assert len(rs) == n
+    doff = _offsets(datas)
+    _, py = _bytes_ptr_keep(keep, y48)
+    _, pr = _bytes_ptr_keep(keep, b"".join(rs))
+    _, pd = _bytes_ptr_keep(keep, b"".join(datas))
+    _, pdo = _u32_keep(keep, doff)
+    ub, pu = _out(48 * n)
+    vb, pv = _out(doff[-1])
+    wb, pw = _out(96 * n)
+    _check(lib().lcb_tpke_encrypt_batch(pu, pv, pw, py, pr, pd, pdo, n), "tpke_encrypt_batch")
+    u, v, w = bytes(ub), _split(bytes(vb), doff), bytes(wb)
+    return [(u[48 * i:48 * i + 48], v[i], w[96 * i:96 * i + 96]) for i in range(n)]
+
+
+def tpke_full_decrypt_batch(problems):
+    """PublicKey.FullDecrypt's combination and keystream for a batch in one call (lcb_tpke_full_decrypt_batch).
+    problems: list of (decryptor ids, their Ui48 shares, V); every share of a problem is combined (x = id + 1).
+    Returns the plaintext, or None where the interpolation fails (a repeated id), per problem."""
+    keep = []
+    n = len(problems)
+    ids = [i for p in problems for i in p[0]]
+    uis = [u for p in problems for u in p[1]]
+    off = _offsets([p[0] for p in problems])
+    voff = _offsets([p[2] for p in problems])
+    pi = _i32_keep(keep, ids)
+    _, pu = _bytes_ptr_keep(keep, b"".join(uis))
+    _, poff = _u32_keep(keep, off)
+    _, pv = _bytes_ptr_keep(keep, b"".join(p[2] for p in problems))
+    _, pvo = _u32_keep(keep, voff)
+    ob, po = _out(voff[-1])
+    sb, ps = _out(n)
+    _check(lib().lcb_tpke_full_decrypt_batch(po, ps, pi, pu, poff, pv, pvo, n), "tpke_full_decrypt_batch")
+    pts = _split(bytes(ob), voff)
+    return [pts[j] if sb[j] else None for j in range(n)]
+
+
+def kdf_phase_ms():
+    """Device time (ms) of k_kdf_xor in this thread's last host-pointer keystream call (lcb_kdf_phase_ms)."""
+    ms = (ctypes.c_float * 1)()
+    _check(lib().lcb_kdf_phase_ms(ms), "kdf_phase_ms")
+    return float(ms[0])
 
 
 def dkg_commitment_eval(commitments, degree, queries):

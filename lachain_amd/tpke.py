@@ -10,8 +10,9 @@ liblachain_bls.so.  Class / method names and error behaviour follow the referenc
   TrustedKeyGen             TPKE/TrustedKeyGen.cs:11-34 (degree-(f-1) polynomial, f coefficients)
   Utils.XorWithHash / HashToG2  TPKE/Utils.cs:12-27
 
-Batch entry points (`VerifyShares`, `DecryptBatch`) hand whole batches to the GPU in one call — the
-shape HoneyBadger's loops can use (HoneyBadger.cs:141-175, 200-247).
+Batch entry points (`VerifyShares`, `DecryptBatch`, `EncryptBatch`, `FullDecryptBatch`, `Utils.XorWithHashBatch`) hand
+whole batches to the GPU in one call — the shape HoneyBadger's loops can use (HoneyBadger.cs:141-175, 200-247).  The
+single-item `Encrypt` / `FullDecrypt` / `XorWithHash` keep the host keystream, which is faster for one item.
 """
 import struct
 
@@ -63,6 +64,11 @@ class Utils:
     @staticmethod
     def XorWithHash(g1_bytes: bytes, data: bytes) -> bytes:
         return native.xor_with_hash(g1_bytes, data)
+
+    @staticmethod
+    def XorWithHashBatch(g1_bytes_list, datas):
+        """XorWithHash for a batch in one call, on the device keystream"""
+        return native.xor_with_hash_batch([bytes(g) for g in g1_bytes_list], [bytes(d) for d in datas])
 
     @staticmethod
     def HashToG2(u_bytes: bytes, v: bytes) -> bytes:
@@ -132,6 +138,28 @@ class PublicKey:
         if u is None:
             raise ValueError("LagrangeInterpolate failed")
         return RawShare(Utils.XorWithHash(u, share.V), share.Id)
+
+    def EncryptBatch(self, raw_shares, rs=None):
+        """Encrypt for a batch in one call (U, the device keystream and W on one stream; T = rY stays on the device)"""
+        rs = list(rs) if rs is not None else [Fr.GetRandom() for _ in raw_shares]
+        res = native.tpke_encrypt_batch(self._y, [r.ToBytes() for r in rs], [s.ToBytes() for s in raw_shares])
+        return [EncryptedShare(u, v, w, s.Id) for (u, v, w), s in zip(res, raw_shares)]
+
+    def FullDecryptBatch(self, shares, partial_lists):
+        """FullDecrypt for a batch in one call: partial_lists[i] are the PartiallyDecryptedShares of shares[i].  Returns
+        RawShare, or None where FullDecrypt throws (too few shares, a repeated DecryptorId, a ShareId mismatch, a failed
+        interpolation), per item."""
+        good = []
+        for i, (share, us) in enumerate(zip(shares, partial_lists)):
+            ids = [p.DecryptorId for p in us]
+            if len(us) >= self._t and len(set(ids)) == len(ids) and all(p.ShareId == share.Id for p in us):
+                good.append(i)
+        out = [None] * len(shares)
+        res = native.tpke_full_decrypt_batch([([p.DecryptorId for p in partial_lists[i]],
+                                               [p.Ui for p in partial_lists[i]], shares[i].V) for i in good])
+        for i, pt in zip(good, res):
+            out[i] = RawShare(pt, shares[i].Id) if pt is not None else None
+        return out
 
     def ToBytes(self):
         return struct.pack("<i", self._t) + self._y
