@@ -781,6 +781,58 @@ int lcb_block_txs_verify_dev(uint8_t *accept, uint8_t *detail, uint8_t *root_ok,
 int lcb_ctx_tx_phase_ms(lcb_ctx *ctx, float ms[3]);
 int lcb_tx_phase_ms(float ms[3]);
 
+/* raw-transaction ingress: the other direction.  n signed wire transactions (RLP) go in; the decoded records,
+   signatures, RawHash, FullHash, the sender and the pool's signature decision come out of one call
+   (TransactionServiceWeb3.SendRawTransaction, TransactionServiceWeb3.cs:184-215, down to TransactionPool.Add's
+   signature check, TransactionPool.cs:130-143).  The decode runs on the device (k_rawtx.hip) and treats every byte as
+   hostile.  Item i is raw[raw_off[i] .. raw_off[i + 1]).  The signature width follows use_new_chain_id (66, else 65).
+   The decoder is strict: status[i] names the first rule an item breaks, and such an item gets zero bytes in every other
+   output; the caller sends it down its host path (what Nethereum's decoder makes of malformed or non-canonical RLP is
+   pinned by no reference vector, and the refusals are a conservative superset of where the reference throws):
+     NOT_LIST     an empty item, or a first byte below c0
+     LIST_LENGTH  a long list header with more than 4 length bytes, running past the item, with a zero first length
+                  byte or a length below 56; or header + payload != the item's length
+     ELEMENT      among the nine elements: a list byte, a header or body running past the payload, 81 before a byte
+                  below 80, a long form with more than 4 length bytes, a zero first length byte or a length below 56
+     COUNT        fewer than nine elements, or bytes left after the ninth (a tenth is never parsed)
+     WIDTH        nonce, gasPrice, gasLimit above 8 bytes; to neither 0 nor 20; value, r, s above 32; v not sig_len - 64
+   Decoded integers are the big-endian value of their bytes (empty: 0); value, r, s are left-padded; sigs_out[i] =
+   r || s || v; inv_span_out[2 i], [2 i + 1] = the invocation's offset in raw and its length (it is not copied).
+   detail[i]: SAME_ENCODING = elements 0-5 as they stand on the wire are Lachain's own encoding of the decoded fields
+   (TransactionUtils.cs:30-48: no leading zero byte in nonce or value, gasPrice / gasLimit not empty and without a
+   leading zero unless the lone byte 00); CHAIN_OK = v is 2 chain_id + 35 or + 36 (:203); RECOVERS = the signature
+   recovers from RawHash (lcb_ecdsa_recover_hashed_batch's rules, no low-s rule).  raw32_out / full32_out: RawHash under
+   chain_id and FullHash of the decoded fields (what SendRawTransaction returns).  accept[i] = status 0 and detail 7;
+   txs_out[i].from is the recovered address where accept[i] is 1, zero otherwise.  status is required, every other
+   output may be null; with accept == NULL the recovery is skipped and detail carries bits 0 and 1 only.
+   A call fails (-1) for a missing status, raw or raw_off, chain_id <= 0, a chain id whose 2 chain_id + 36 does not fit
+   sig_len - 64 bytes (above 109 old, 32749 new) and, in the host-pointer form, for decreasing offsets or an item of 2^31
+   bytes or more; the device forms trust the caller for the offsets (raw_off, txs_out and inv_span_out 8-byte aligned)
+   and trust nothing inside the items.  A bad item never fails a call. */
+#define LCB_RAWTX_OK          0
+#define LCB_RAWTX_NOT_LIST    1
+#define LCB_RAWTX_LIST_LENGTH 2
+#define LCB_RAWTX_ELEMENT     3
+#define LCB_RAWTX_COUNT       4
+#define LCB_RAWTX_WIDTH       5
+#define LCB_RAWTX_SAME_ENCODING 1
+#define LCB_RAWTX_CHAIN_OK      2
+#define LCB_RAWTX_RECOVERS      4
+int lcb_raw_txs_ingest_batch(uint8_t *accept, uint8_t *status, uint8_t *detail, lcb_tx_fields *txs_out,
+                             uint64_t *inv_span_out, uint8_t *sigs_out, uint8_t *raw32_out, uint8_t *full32_out,
+                             const uint8_t *raw, const uint64_t *raw_off, size_t n, int use_new_chain_id, int32_t chain_id);
+int lcb_ctx_raw_txs_ingest_dev(lcb_ctx *ctx, uint8_t *accept, uint8_t *status, uint8_t *detail, lcb_tx_fields *txs_out,
+                               uint64_t *inv_span_out, uint8_t *sigs_out, uint8_t *raw32_out, uint8_t *full32_out,
+                               const uint8_t *raw, const uint64_t *raw_off, size_t n, int use_new_chain_id,
+                               int32_t chain_id, void *stream);
+int lcb_raw_txs_ingest_dev(uint8_t *accept, uint8_t *status, uint8_t *detail, lcb_tx_fields *txs_out,
+                           uint64_t *inv_span_out, uint8_t *sigs_out, uint8_t *raw32_out, uint8_t *full32_out,
+                           const uint8_t *raw, const uint64_t *raw_off, size_t n, int use_new_chain_id, int32_t chain_id,
+                           void *stream);
+/* kernel milliseconds of the context's last ingress: decode and hashing, recovery, finish */
+int lcb_ctx_rawtx_phase_ms(lcb_ctx *ctx, float ms[3]);
+int lcb_rawtx_phase_ms(float ms[3]);
+
 /* ------------------------------------------------------------------ state trie: node hashes, checks, roots
    Block.Header.StateHash is the Keccak-256 of six trie roots (BlockchainSnapshot.cs:71-80); each root is the hash of a
    32-way hash-array-mapped trie (Lachain.Storage/Trie/TrieHashMap.cs, LeafNode.cs, InternalNode.cs):

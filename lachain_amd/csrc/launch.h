@@ -112,6 +112,9 @@ extern "C" void lcbk_keccak256(hipStream_t s, const uint8_t *data, const uint64_
 extern "C" void lcbk_tx_hash(hipStream_t s, const uint8_t *txs, const uint8_t *inv, const uint64_t *off, const uint8_t *sigs, u32 sig_len, const uint8_t *claimed, u32 chain_id, u32 n, uint8_t *raw32, uint8_t *full32, uint8_t *match, uint32_t *long_ws);
 extern "C" void lcbk_tx_detail(hipStream_t s, const uint8_t *match, const uint8_t *rec_ok, const uint8_t *addr20, const uint8_t *txs, u32 n, uint8_t *accept, uint8_t *detail);
 extern "C" void lcbk_tx_root_ok(hipStream_t s, const uint8_t *roots, const uint8_t *expected, u32 n, uint8_t *root_ok);
+// k_rawtx.hip
+extern "C" void lcbk_rawtx_decode(hipStream_t s, const uint8_t *raw, const uint64_t *off, uint64_t span_base, u32 sig_len, u32 chain_id, u32 n, uint8_t *status, uint8_t *detail, uint8_t *txs, uint64_t *span, uint8_t *sigs, uint8_t *raw32, uint8_t *full32, uint32_t *long_ws);
+extern "C" void lcbk_rawtx_finish(hipStream_t s, const uint8_t *status, const uint8_t *rec_ok, const uint8_t *addr20, const uint8_t *det_in, u32 n, uint8_t *accept, uint8_t *detail, uint8_t *txs);
 extern "C" void lcbk_trie_flat(hipStream_t s, const uint8_t *nodes, const uint8_t *data, const uint64_t *off, const uint8_t *expected32, u32 n, uint8_t *out32, uint8_t *accept, uint32_t *list_ws);
 extern "C" void lcbk_trie_level(hipStream_t s, uint8_t *hashes32, const uint8_t *nodes, const uint8_t *data, const uint64_t *off, const uint64_t *child_off, const int64_t *child_ref, const uint8_t *literals32, const uint64_t *order, u32 count);
 extern "C" size_t lcbk_trie_root_ws_bytes(u32 n, u32 B);

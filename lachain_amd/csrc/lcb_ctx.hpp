@@ -176,6 +176,15 @@ enum TxBuf {          // lcb_ctx::tx, transaction hashing and receipts (n transa
     TX_LONG,          // the count and list of long items k_tx_hash leaves to k_tx_hash_long, n + 1 words; hash_enqueue
     TX_N
 };
+enum RawTxBuf {       // lcb_ctx::rawtx, the raw-transaction ingress (n items)
+    RAWTX_HASH,       // the raw hashes the recovery reads when the caller takes none, 32 n B; ingest_enqueue
+    RAWTX_SIGS,       // the decoded signatures when the caller takes none, sig_len n B; the same
+    RAWTX_DETAIL,     // detail bits 0 and 1 when the caller takes no detail, n B; the same
+    RAWTX_REC_OK,     // the recovery's validity, n B; the same
+    RAWTX_ADDR,       // the recovered addresses, 20 n B; the same
+    RAWTX_LONG_LIST,  // the count and list of long items k_rawtx_decode leaves to k_rawtx_long, n + 1 words; the same
+    RAWTX_N
+};
 enum TrieBuf {        // lcb_ctx::trie, the state trie
     TRIE_LIST,        // the flat call's count and list of internal nodes, n + 1 words; flat_enqueue
     TRIE_ROOT_WS,     // the root builder's workspace (lcbk_trie_root_ws_bytes); root_enqueue
@@ -295,6 +304,10 @@ struct lcb_ctx {
     DevBuf tx[TX_N];
     hipEvent_t tx_ev[4] = {};         // around hashing / recovery and decision / roots of the last call
     bool tx_ev_ready = false, tx_ran = false;
+    // raw-transaction ingress (lcb_rawtx.cpp)
+    DevBuf rawtx[RAWTX_N];
+    hipEvent_t rawtx_ev[4] = {};      // around decode and hashing / recovery / finish of the last call
+    bool rawtx_ev_ready = false, rawtx_ran = false;
     // state trie (lcb_trie.cpp)
     DevBuf trie[TRIE_N];
     // TPKE keystream and the one-call Encrypt / FullDecrypt (lcb_kdf.cpp)

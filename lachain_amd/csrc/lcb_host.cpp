@@ -393,6 +393,7 @@ void ctx_free(lcb_ctx *c) {
     lcb_int::ecdsa_ctx_release(c);
     lcb_int::ecies_ctx_release(c);
     lcb_int::txhash_ctx_release(c);
+    lcb_int::rawtx_ctx_release(c);
     lcb_int::trie_ctx_release(c);
     lcb_int::kdf_ctx_release(c);
     if (c->ver_ev_ready) for (auto &e : c->ver_ev) (void)hipEventDestroy(e);

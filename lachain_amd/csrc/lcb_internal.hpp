@@ -33,6 +33,7 @@ extern int g_orig_cofactor;           // lcb_set_original_g2_cofactor: the hashi
 void ecdsa_ctx_release(lcb_ctx *c);   // lcb_ecdsa.cpp: the context's cached key set
 void ecies_ctx_release(lcb_ctx *c);   // lcb_ecies.cpp: the envelope workspaces and events
 void txhash_ctx_release(lcb_ctx *c);  // lcb_txhash.cpp: the transaction workspaces and events
+void rawtx_ctx_release(lcb_ctx *c);   // lcb_rawtx.cpp: the raw-transaction ingress's workspaces and events
 void trie_ctx_release(lcb_ctx *c);    // lcb_trie.cpp: the state-trie workspaces
 void kdf_ctx_release(lcb_ctx *c);     // lcb_kdf.cpp: the keystream compositions' workspaces and events
 

@@ -7,6 +7,7 @@ import ctypes
 import os
 import struct
 import threading
+from typing import NamedTuple, Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LCB_LIB_PATH selects another build of the same library (A/B timing of kernel variants)
@@ -267,6 +268,11 @@ _SIGS = {
                                                                         ctypes.c_void_p, ctypes.c_void_p, c_size,
                                                                         ctypes.c_int, ctypes.c_int32, ctypes.c_void_p]),
     "lcb_tx_phase_ms": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float)]),
+    "lcb_raw_txs_ingest_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u64p, c_u8p, c_u8p, c_u8p, c_u8p, c_u64p,
+                                                c_size, ctypes.c_int, ctypes.c_int32]),
+    "lcb_raw_txs_ingest_dev": (ctypes.c_int, [ctypes.c_void_p] * 10 + [c_size, ctypes.c_int, ctypes.c_int32,
+                                                                       ctypes.c_void_p]),
+    "lcb_rawtx_phase_ms": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float)]),
     "lcb_trie_node_hash_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u64p, c_u8p, c_size]),
     "lcb_trie_node_hash_dev": (ctypes.c_int, [ctypes.c_void_p] * 6 + [c_size, ctypes.c_void_p]),
     "lcb_trie_rehash_batch": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u64p, c_u64p, ctypes.POINTER(ctypes.c_int64), c_u8p,
@@ -297,7 +303,8 @@ for _name in ("tpke_prepare_dev", "tpke_verify_prepared_dev", "tpke_verify_prepa
               "ecdsa_special_recover_hashed_dev", "tx_verify_dev", "ecdsa_recover_phase_ms", "keccak256_dev",
               "rbc_check_echo_dev", "rbc_merkle_tree_dev", "merkle_root_dev", "secp_ecdh_dev", "aes256_gcm_encrypt_dev",
               "aes256_gcm_decrypt_dev", "secp256k1_encrypt_dev", "secp256k1_decrypt_dev", "ecies_phase_ms", "tx_hash_dev",
-              "receipts_verify_dev", "block_txs_verify_dev", "tx_phase_ms", "trie_node_hash_dev", "trie_rehash_dev",
+              "receipts_verify_dev", "block_txs_verify_dev", "tx_phase_ms", "raw_txs_ingest_dev", "rawtx_phase_ms",
+              "trie_node_hash_dev", "trie_rehash_dev",
               "trie_root_dev", "xor_with_hash_dev", "tpke_encrypt_dev", "tpke_full_decrypt_dev", "kdf_phase_ms"):
     _res, _args = _SIGS["lcb_" + _name]
     _SIGS["lcb_ctx_" + _name] = (_res, [ctypes.c_void_p] + list(_args))
@@ -898,6 +905,55 @@ def tx_phase_ms():
     """kernel milliseconds of the calling thread's last transaction call: [hashing, recovery and decision, roots]"""
     ms = (ctypes.c_float * 3)()
     _check(lib().lcb_tx_phase_ms(ms), "tx_phase_ms")
+    return list(ms)
+
+
+# ---------------------------------------------------------------- raw-transaction ingress
+RAWTX_OK, RAWTX_NOT_LIST, RAWTX_LIST_LENGTH, RAWTX_ELEMENT, RAWTX_COUNT, RAWTX_WIDTH = range(6)
+RAWTX_SAME_ENCODING, RAWTX_CHAIN_OK, RAWTX_RECOVERS = 1, 2, 4
+
+
+class RawTxs(NamedTuple):
+    """the outputs of raw_txs_ingest_batch over n items: accept (None without the recovery), status and detail are
+    n bytes; records n lcb_tx_fields (104 B each); spans n (offset in the joined raw bytes, length) pairs; sigs
+    n x sig_len bytes; raw32 and full32 n x 32 bytes"""
+    accept: Optional[bytes]
+    status: bytes
+    detail: bytes
+    records: bytes
+    spans: list
+    sigs: bytes
+    raw32: bytes
+    full32: bytes
+
+
+def raw_txs_ingest_batch(raws, use_new_chain_id: bool, chain_id: int, recover: bool = True) -> RawTxs:
+    """lcb_raw_txs_ingest_batch over the signed wire transactions `raws` (byte strings): decode, RawHash, FullHash and,
+    with recover, the sender recovery and the accept decision (accept = status 0 and detail 7), all on the device"""
+    n = len(raws)
+    keep = []
+    sig_len = 66 if use_new_chain_id else 65
+    _, pr = _bytes_ptr_keep(keep, b"".join(raws))
+    po = _u64_keep(keep, _offsets(raws))
+    ab, pa = _out(n)
+    sb, ps = _out(n)
+    db, pd = _out(n)
+    tb, pt = _out(TX_FIELDS_BYTES * n)
+    spans = (ctypes.c_uint64 * max(1, 2 * n))()
+    gb, pg = _out(sig_len * n)
+    rb, prh = _out(32 * n)
+    fb, pf = _out(32 * n)
+    _check(lib().lcb_raw_txs_ingest_batch(pa if recover else None, ps, pd, pt, spans, pg, prh, pf, pr, po, n,
+                                          int(bool(use_new_chain_id)), chain_id), "raw_txs_ingest_batch")
+    return RawTxs(bytes(ab)[:n] if recover else None, bytes(sb)[:n], bytes(db)[:n], bytes(tb)[:TX_FIELDS_BYTES * n],
+                  [(spans[2 * i], spans[2 * i + 1]) for i in range(n)], bytes(gb)[:sig_len * n], bytes(rb)[:32 * n],
+                  bytes(fb)[:32 * n])
+
+
+def rawtx_phase_ms():
+    """kernel milliseconds of the calling thread's last ingress: [decode and hashing, recovery, finish]"""
+    ms = (ctypes.c_float * 3)()
+    _check(lib().lcb_rawtx_phase_ms(ms), "rawtx_phase_ms")
     return list(ms)
 
 

@@ -4,10 +4,11 @@ RawHash, FullHash, the hash check, the sender recovery and the From comparison r
 
 Reference: src/Lachain.Crypto/TransactionUtils.cs (GetEthTx, Rlp, RlpWithSignature, RawHash, FullHash),
 src/Lachain.Core/Blockchain/Operations/TransactionSigner.cs and TransactionVerifier.cs (VerifyTransactionImmediately,
-VerifyTransactions and the public-key cache).  Rlp and RlpWithSignature are host byte code (wire use and tests); every
+VerifyTransactions and the public-key cache), and src/Lachain.Core/RPC/HTTP/Web3/TransactionServiceWeb3.cs:69-82, :184-254
+(MakeTransaction, SendRawTransaction and its batch forms: wire bytes in, decoded on the device).  Rlp and RlpWithSignature are host byte code (wire use and tests); every
 hash and every curve operation is the library's.
 """
-from typing import Dict, List, NamedTuple, Sequence
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 from . import native
 
@@ -203,3 +204,57 @@ class TransactionVerifier:
             for (i, _), a in zip(cached, acc):
                 out[i] = bool(a)
         return out
+
+
+RAWTX_STATUS_NAMES = ("Ok", "NotList", "ListLength", "Element", "Count", "Width")
+
+
+def MakeTransactions(raws: Sequence[bytes], use_new_chain_id: bool) -> List[Optional[Tuple[Transaction, bytes]]]:
+    """TransactionServiceWeb3.MakeTransaction (:69-82) and the padded signature of SendRawTransaction (:189-198) for each
+    signed wire transaction, from one lcb_raw_txs_ingest_batch call: (Transaction, r || s || v), or None where the strict
+    decoder refuses the item.  From is the sender recovered on the device where the pool's signature check would pass
+    (native.RawTxs.accept) and 20 zero bytes otherwise: the reference takes it from Nethereum's own recovery."""
+    return [None if m is None else (m[0], m[1]) for m in _ingest(raws, use_new_chain_id)[0]]
+
+
+def _ingest(raws, use_new_chain_id):
+    chain = TransactionUtils.ChainId(use_new_chain_id)
+    size = _signature_size(use_new_chain_id)
+    joined = b"".join(raws)
+    got = native.raw_txs_ingest_batch(raws, use_new_chain_id, chain)
+    made = []
+    for i in range(len(raws)):
+        if got.status[i] != native.RAWTX_OK:
+            made.append(None)
+            continue
+        rec = got.records[104 * i:104 * (i + 1)]
+        at, ln = got.spans[i]
+        t = Transaction(To=rec[56:56 + int.from_bytes(rec[96:100], "little")], Value=rec[24:56], From=rec[76:96],
+                        Nonce=int.from_bytes(rec[0:8], "little"), GasPrice=int.from_bytes(rec[8:16], "little"),
+                        GasLimit=int.from_bytes(rec[16:24], "little"), Invocation=joined[at:at + ln])
+        made.append((t, got.sigs[size * i:size * (i + 1)], got.full32[32 * i:32 * i + 32]))
+    return made, got
+
+
+def SendRawTransactionBatch(raw_txs: Sequence[bytes], use_new_chain_id: bool,
+                            pool_add: Callable[[Transaction, bytes], str]) -> List[str]:
+    """la_sendRawTransactionBatch (TransactionServiceWeb3.cs:217-235): SendRawTransaction (:184-215) per item, in list
+    order, over one device call.  Per item: "0x" + FullHash where the transaction entered the pool; "BadChainId" (:203);
+    "InvalidSignature" where TransactionPool.Add's signature check fails (TransactionPool.cs:130-143); the string
+    pool_add returned where it is not "Ok"; "Refused: <status>" where the strict decoder turns the bytes down (the
+    caller sends those down its host path).  pool_add(transaction, signature) stands for the pool's own state checks
+    (nonce, balance, gas, duplicates) and returns an OperatingError name; it is called only for items whose signature
+    check passed."""
+    made, got = _ingest(raw_txs, use_new_chain_id)
+    out = []
+    for i, m in enumerate(made):
+        if m is None:
+            out.append("Refused: " + RAWTX_STATUS_NAMES[got.status[i]])
+        elif not got.detail[i] & native.RAWTX_CHAIN_OK:
+            out.append("BadChainId")
+        elif not got.accept[i]:
+            out.append("InvalidSignature")
+        else:
+            result = pool_add(m[0], m[1])
+            out.append("0x" + m[2].hex() if result == "Ok" else result)
+    return out
