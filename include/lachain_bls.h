@@ -442,6 +442,26 @@ int lcb_debug_asm_tower(int op, const uint32_t *a, const uint32_t *b, size_t n, 
    op 13: the comb's signed 8-bit digits of a -> digits, 36 signed bytes.
    op 14: 2 a, op 15: a + affine b, op 16: a + b -> (x, y, z, inf); an infinite result has zero coordinates. */
 int lcb_debug_secp_op(int op, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out);
+/* test hook: one routine under G2.SetHashOf, or one device point decoder, on n (1..65536) arbitrary items, one lane each.
+   in, 48 words per item; out, 76 words per item: value words [0, 72), out[72] = the routine's flag, out[73] = 1 for a
+   decoded point at infinity, the rest zero.  A field operand is 12 little-endian 32-bit words in Montgomery form (m =
+   a 2^384 mod p, below p; the convention of lcb_debug_fp12), an Fp2 operand a[12] b[12]; byte strings are packed
+   little-endian into the words.
+   op 0: fp_sqrt of in[0..12) -> a^((p+1)/4) at [0, 12), flag = it is a root.
+   op 1: fp2_sqrt of in[0..24) -> mcl's root at [0, 24), flag = a root exists (zero words without one).
+   op 2: fp2_sqrt_any, the same layout: a root of either sign.
+   op 3: fp2_sqrt_normed: flag = the norm is a square; then the root (mcl's) at [0, 24), from the norm's root as the
+         map forms it; zero words otherwise (the routine is not run on a non-square).
+   op 4: fp_inv_gcd of in[0..12) -> [0, 12) (0 -> 0).   op 5: fp2_inv_g of in[0..24) -> [0, 24).
+   op 6: Fp::setHashOf's reduction of a 64-byte SHA-512 digest (in[0..16)) -> t at [0, 12).
+   op 7: MapTo::calcBN of t = in[0..24) -> affine x at [0, 24), y at [24, 48), flag = a point was found.
+   op 8: the Budroni-Pintore cofactor clearing, op 9: multiplication by the original cofactor h2, of the affine twist
+         point x = in[0..24), y = in[24..48) -> Jacobian (X, Y, Z) at [0, 72); Z = 0 is the point at infinity.
+   op 10: the device G1 decoder on 48 bytes -> affine x at [0, 12), y at [12, 24); op 11: the device G2 decoder on 96
+          bytes -> x at [0, 24), y at [24, 48); flag = accepted, out[73] = infinity (zero coordinates).
+   op 12: mclBnG2_hashAndMapTo's second kernel (the four-lane cofactor clearing) alone, once per item, on the mapped
+          point (x, y, 1) given as for op 8 -> Jacobian at [0, 72), flag = 1. */
+int lcb_debug_h2g2_op(int op, const uint32_t *in, size_t n, uint32_t *out);
 /* test hook: lcb_tpke_verify_shares up to its Miller loop (the one-lane kernel) for n (1..65536) shares, without the
    final exponentiation: f_out = each share's Miller value (144 x u32), ok_out = its validity flag */
 int lcb_debug_tpke_miller(uint32_t *f_out, uint8_t *ok_out, size_t n, const uint8_t *y_keys, size_t n_keys,

@@ -591,7 +591,13 @@ DN bool g2_decompress(g2a &out, const uint8_t *b) {
     fp2_mul(t, t, x);
     fp2_load_const(b2, LCB_B2);
     fp2_add(t, t, b2);
-    if (!fp2_sqrt_any(y, t)) return false;            // the sign is fixed below, so any root serves
+    // The flag fixes the sign wherever the flagged coordinate of y is non-zero (its two candidates differ in parity), so
+    // either root serves there.  It cannot where that coordinate is zero: then y^2 = t lies in Fp (t.b == 0; y = (0, s)
+    // for a non-residue t.a, y = (s, 0) under the other convention for a residue), parity(0) = 0 for both roots, and
+    // flag 0 / flag 1 decode to THIS root / its negative — two different points that both serialise with flag 0.
+    // fp2_sqrt_any returns fp2_sqrt's root (mcl's) for t.b == 0, so the point is the one the host decoder, the oracle
+    // and the model land on (tests/test_gpu_h2g2_edges.py, the y-coordinate-zero encodings).
+    if (!fp2_sqrt_any(y, t)) return false;
     if (fp_is_odd(g2_sign_coord(y)) != odd) fp2_neg(y, y);
     out.x = x; out.y = y; out.inf = false;
     return true;

@@ -7,7 +7,8 @@
 //   P   = MapTo::calcBN<G2, Fp2>(t)  (Fouque-Tibouchi / Shallue-van de Woestijne, mcl root choices)
 //   H   = Budroni-Pintore cofactor clearing (z^2 - z - 1)P + psi((z - 1)P) + psi^2(2P)
 // The algorithm is restated from mcl and is UNPINNED by any reference vector; the
-// oracle (oracle/bls.c:g2_hash) implements the same steps independently.
+// oracle (oracle/bls.c:g2_hash) implements the same steps independently, and every routine below is compared with the
+// Python model branch by branch through the test hook of h2g2_debug.hpp (tests/test_gpu_h2g2_edges.py).
 #pragma once
 #include "curve.hpp"
 

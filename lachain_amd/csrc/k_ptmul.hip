@@ -128,6 +128,10 @@ template <class LT> DI void pt_mul_u64(LT *L, g2 &r, const g2 &p, u64 k) {   // 
     }
     r = acc;
 }
+// Any point of the twist is a legal P, not only the map's outputs: pt_add (coop_pt.hpp) is complete — either input at
+// infinity, P == Q (doubling) and P == -Q (infinity), as jac_add — and pt_dbl keeps Z = 0, so the ladders pass through
+// infinity and back.  tests/test_gpu_h2g2_edges.py drives k_mcl_g2_clear with points of order 13, 23 and 2713; on order
+// 13 both ladders double infinity, add to infinity and add P to -P (tests/test_h2g2_ref.py asserts that they do).
 template <class LT> DI void pt_clear_cofactor_bp(LT *L, g2 &Q, const g2 &P) {   // h2g2.hpp g2_clear_cofactor_bp
     // with A = (z - 1) P = -[|z| + 1] P: Q = -[|z|] A + (psi^2(2P) - P) + psi(A); three points live at a time
     g2 V, A, W;
@@ -176,6 +180,25 @@ extern "C" __global__ void __launch_bounds__(64, 1) k_mcl_g2_clear(u32 *io) {
     pt_clear_cofactor_bp(lds + threadIdx.x / PT_LANES, H, P);
     __syncthreads();
     if (threadIdx.x == 0) *(g2 *)io = H;
+}
+// ------------------------------------------------------------------------------------------------ test hook
+// one routine under hash-to-G2, or one point decoder, per lane on arbitrary operands (h2g2_debug.hpp has the layout)
+#include "h2g2_debug.hpp"
+extern "C" __global__ void __launch_bounds__(64, 1) k_h2g2_debug(int op, const u32 *in, u32 n, u32 *out) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    h2g2_debug_op(op, in + (size_t)H2G2_DEBUG_IN * i, out + (size_t)H2G2_DEBUG_OUT * i);
+}
+extern "C" size_t lcbk_h2g2_debug_in_words(void) { return H2G2_DEBUG_IN; }
+extern "C" size_t lcbk_h2g2_debug_out_words(void) { return H2G2_DEBUG_OUT; }
+extern "C" int lcbk_h2g2_debug_ops(void) { return H2G2_DEBUG_OPS; }
+extern "C" void lcbk_h2g2_debug(hipStream_t s, int op, const u32 *in, u32 n, u32 *out) {
+    if (!n) return;
+    LCB_LAUNCH_GATED(k_h2g2_debug, dim3((n + 63) / 64), dim3(64), 0, s, op, in, n, out);
+}
+// k_mcl_g2_clear alone on a mapped point the caller preset (io[0..72) Jacobian, io[249] = 1): lcb_debug_h2g2_op's op 12
+extern "C" void lcbk_mcl_g2_clear(hipStream_t s, u32 *io) {
+    LCB_LAUNCH_GATED(k_mcl_g2_clear, dim3(1), dim3(64), 0, s, io);
 }
 extern "C" void lcbk_mcl_g2_hash(hipStream_t s, u32 *io, int orig_cof) {
     LCB_LAUNCH_GATED(k_mcl_g2_hash, dim3(1), dim3(64), 0, s, io, orig_cof);

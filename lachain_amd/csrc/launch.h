@@ -16,6 +16,13 @@ extern "C" void lcbk_tpke_ct_prepare_hw(hipStream_t s, const uint8_t *cts_u, con
 extern "C" void lcbk_ct_ok_merge(hipStream_t s, uint8_t *ct_ok, const uint8_t *h_ok, u32 c0, u32 c1);
 extern "C" void lcbk_lineset_fill(dim3 grid, hipStream_t s, u32 *lines, u32 n_sets, const u32 *sets, uint8_t *w_g2);
 extern "C" void lcbk_mcl_g2_hash(hipStream_t s, u32 *io, int orig_cof);
+// test hook (lcb_debug_h2g2_op): one routine under hash-to-G2 or one point decoder per lane; items of
+// lcbk_h2g2_debug_in_words() / _out_words() words.  lcbk_mcl_g2_clear: k_mcl_g2_clear alone on a preset io block
+extern "C" size_t lcbk_h2g2_debug_in_words(void);
+extern "C" size_t lcbk_h2g2_debug_out_words(void);
+extern "C" int lcbk_h2g2_debug_ops(void);
+extern "C" void lcbk_h2g2_debug(hipStream_t s, int op, const u32 *in, u32 n, u32 *out);
+extern "C" void lcbk_mcl_g2_clear(hipStream_t s, u32 *io);
 extern "C" void lcbk_lineset_coop(hipStream_t s, u32 *lines, u32 n_sets, const u32 *sets, uint8_t *w_g2);
 // the same at two waves per SIMD (k_prep.hip): the census ciphertexts of the fused batched verify
 extern "C" void lcbk_lineset_coop_2w(hipStream_t s, u32 *lines, u32 n_sets, const u32 *sets, uint8_t *w_g2);

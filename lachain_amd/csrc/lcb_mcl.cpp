@@ -553,6 +553,47 @@ extern "C" int lcb_debug_fp12(int which, const uint32_t in[144], uint32_t out[14
     memcpy(out, IOH, 576);
     return 0;
 }
+// test hook: one routine under hash-to-G2, or one device point decoder, on n items, one lane each (k_h2g2_debug;
+// h2g2_debug.hpp and include/lachain_bls.h have the layout: 48 words in, 76 words out per item).  Op 12 is no routine of
+// that kernel: it runs k_mcl_g2_clear alone, once per item, on the mapped point (x, y, 1) — the second kernel of
+// mclBnG2_hashAndMapTo with a chosen point in place of the first kernel's
+extern "C" int lcb_debug_h2g2_op(int op, const uint32_t *in, size_t n, uint32_t *out) {
+    SYNC_CTX_OR(c, -1)
+    if (!n || n > 65536) { set_err("debug h2g2 op: 1..65536 items"); return -1; }
+    const int n_ops = lcbk_h2g2_debug_ops();
+    if (op < 0 || op > n_ops) { set_err("debug h2g2 op: unknown operation"); return -1; }
+    if (!in || !out) { set_err("debug h2g2 op: missing operand"); return -1; }
+    const size_t iw = lcbk_h2g2_debug_in_words(), ow = lcbk_h2g2_debug_out_words();
+    HostCall h(c, "debug h2g2 op");
+    if (op < n_ops) {
+        const u32 *din = h.in(in, iw * n);
+        u32 *dout = h.out<u32>(ow * n);
+        if (!h.ok()) return -1;
+        lcbk_h2g2_debug(h.s, op, din, (u32)n, dout);
+        if (!launch_ok("debug h2g2 op launch")) return -1;
+        h.back(out, dout, 4 * ow * n);
+        return h.finish();
+    }
+    const size_t blk = 256;                           // one io block per item: the point at [0, 72), the flag at 249
+    std::vector<u32> io(blk * n, 0u);
+    for (size_t i = 0; i < n; i++) {
+        memcpy(&io[blk * i], in + iw * i, 48 * 4);
+        memcpy(&io[blk * i + 48], LCB_ONE_HOST, 48);
+        io[blk * i + 249] = 1u;
+    }
+    u32 *dio = h.work(io.data(), blk * n);
+    if (!h.ok()) return -1;
+    for (size_t i = 0; i < n; i++) lcbk_mcl_g2_clear(h.s, dio + blk * i);
+    if (!launch_ok("debug h2g2 op launch")) return -1;
+    h.back(io.data(), dio, 4 * blk * n);
+    if (h.finish()) return -1;
+    memset(out, 0, 4 * ow * n);
+    for (size_t i = 0; i < n; i++) {
+        memcpy(out + ow * i, &io[blk * i], 72 * 4);
+        out[ow * i + 72] = 1u;
+    }
+    return 0;
+}
 extern "C" void mclBnGT_mul(mclBnGT *z, const mclBnGT *x, const mclBnGT *y) {
     fph::fp12 t;
     fph::mul(t, *(const fph::fp12 *)x, *(const fph::fp12 *)y);

@@ -122,6 +122,8 @@ _SIGS = {
                                            ctypes.POINTER(ctypes.c_uint32), c_size, ctypes.POINTER(ctypes.c_uint32)]),
     "lcb_debug_secp_op": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_uint32),
                                          ctypes.POINTER(ctypes.c_uint32), c_size, ctypes.POINTER(ctypes.c_uint32)]),
+    "lcb_debug_h2g2_op": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), c_size,
+                                         ctypes.POINTER(ctypes.c_uint32)]),
     "lcb_debug_tpke_miller": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32), c_u8p, c_size, c_u8p, c_size, c_u8p, c_u8p,
                                              c_u8p, c_u32p, c_size, c_u32p, c_u32p, c_u8p]),
     "lcb_batched_census": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32)]),
@@ -1579,6 +1581,27 @@ def debug_secp_op(op, a_items, b_items=None):
     out = (ctypes.c_uint32 * (SECP_DEBUG_OUT * n))()
     _check(lib().lcb_debug_secp_op(SECP_DEBUG_OPS[op], a, b, n, out), "debug_secp_op")
     return [list(out[SECP_DEBUG_OUT * i:SECP_DEBUG_OUT * (i + 1)]) for i in range(n)]
+
+
+H2G2_DEBUG_OPS = {"fp_sqrt": 0, "fp2_sqrt": 1, "fp2_sqrt_any": 2, "fp2_sqrt_normed": 3, "fp_inv_gcd": 4, "fp2_inv_g": 5,
+                  "fp_set_hash_digest": 6, "g2_calc_bn": 7, "g2_clear_cofactor_bp": 8, "g2_clear_cofactor_h2": 9,
+                  "g1_decompress": 10, "g2_decompress": 11, "k_mcl_g2_clear": 12}
+H2G2_DEBUG_IN, H2G2_DEBUG_OUT = 48, 76
+
+
+def debug_h2g2_op(op, items):
+    """one routine under hash-to-G2 or one device point decoder (lcb_debug_h2g2_op; op: a key of H2G2_DEBUG_OPS) on
+    items of up to 48 words (shorter ones are zero-padded) -> the 76-word results (value[72] flag inf 0 0),
+    include/lachain_bls.h"""
+    n = len(items)
+    flat = []
+    for v in items:
+        assert len(v) <= H2G2_DEBUG_IN
+        flat += list(v) + [0] * (H2G2_DEBUG_IN - len(v))
+    a = (ctypes.c_uint32 * (H2G2_DEBUG_IN * n))(*flat)
+    out = (ctypes.c_uint32 * (H2G2_DEBUG_OUT * n))()
+    _check(lib().lcb_debug_h2g2_op(H2G2_DEBUG_OPS[op], a, n, out), "debug_h2g2_op")
+    return [list(out[H2G2_DEBUG_OUT * i:H2G2_DEBUG_OUT * (i + 1)]) for i in range(n)]
 
 
 def debug_tpke_miller(y_keys, cts, shares):

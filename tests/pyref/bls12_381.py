@@ -22,7 +22,8 @@ Z = -0xD201000000010000
 
 # ------------------------------------------------------------------------------------------------ Fp, Fp2
 def inv(a):
-    return pow(a, P - 2, P)
+    """a^-1 mod p, 0 for 0 (the value of a^(p-2), by the built-in modular inverse)"""
+    return pow(a, -1, P) if a % P else 0
 
 
 def sqrt_fp(a):
@@ -237,7 +238,10 @@ def g1_to_bytes(p):
     return bytes(b)
 
 
-def g2_from_bytes(b):
+def g2_from_bytes(b, sign_b=False):
+    """sign_b: the flag is the parity of y.b instead of y.a (the library's lcb_set_g2_sign_from_b).  The flag negates
+    f2sqrt's root when the parities differ, so where the flagged coordinate of y is zero (parity 0 under either sign)
+    flag 0 decodes f2sqrt's root and flag 1 its negative: two points that both serialise with flag 0"""
     if b == bytes(96):
         return None
     odd = b[95] >> 7
@@ -249,7 +253,7 @@ def g2_from_bytes(b):
     y = f2sqrt(f2add(f2mul(f2mul(x, x), x), B2))
     if y is None:
         raise ValueError("not on curve")
-    if (y[0] & 1) != odd:                  # sign flag = parity of y.a
+    if (y[1 if sign_b else 0] & 1) != odd:  # sign flag = parity of y.a
         y = f2neg(y)
     return (x, y)
 
@@ -268,13 +272,18 @@ _SQRT_M3 = pow((-3) % P, (P + 1) // 4, P)
 _HALF_M1_SQRT_M3 = (_SQRT_M3 - 1) * inv(2) % P
 
 
-def fp_hash_of(msg):
-    """mcl Fp::setHashOf: SHA-512, first 48 bytes little-endian, keep 381 bits, 380 if still >= p"""
-    d = hashlib.sha512(msg).digest()
+def fp_from_digest(d):
+    """the reduction of mcl Fp::setHashOf on a 64-byte digest: first 48 bytes little-endian, keep 381 bits, 380 if
+    still >= p"""
     v = int.from_bytes(d[:48], "little") & ((1 << 381) - 1)
     if v >= P:
         v &= (1 << 380) - 1
     return v
+
+
+def fp_hash_of(msg):
+    """mcl Fp::setHashOf: SHA-512, then fp_from_digest"""
+    return fp_from_digest(hashlib.sha512(msg).digest())
 
 
 def _legendre(a):

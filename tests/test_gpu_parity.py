@@ -290,3 +290,112 @@ def test_decompression_validity_matches_oracle(mcl):
                 n_ok += 1
                 assert got.ToBytes() == b
         assert n_ok >= 2
+
+
+def test_decompression_validity_device_matches_host_and_oracle(nat, mcl):
+    """the encodings of the test above, and the edge encodings of tests/h2g2_cases.py, through the DEVICE decoders
+    (curve.hpp g1_decompress / g2_decompress; the test above reaches fp_host.hpp's): the hook reports per item, as does
+    lcb_g1_to_affine_dev's ok array.  Device, host and oracle accept the same set."""
+    import torch
+    import h2g2_cases as C
+    rnd = C.parity_encodings(o)
+    dev = torch.device("cuda", 0)
+    for P, size, op, valid, edge in ((mcl.G1, 48, "g1_decompress", o.g1_valid, C.g1_encodings()),
+                                     (mcl.G2, 96, "g2_decompress", o.g2_valid, C.g2_encodings())):
+        encs = rnd[size] + [b for _, b in edge]
+        got = [bool(g[72]) for g in nat.debug_h2g2_op(op, [C.bytes_item(b) for b in encs])]
+        host = []
+        for b in encs:
+            try:
+                P.FromBytes(b)
+                host.append(True)
+            except ValueError:
+                host.append(False)
+        want = [valid(b) for b in encs]
+        assert got == want and host == want, P.__name__
+        assert 2 <= sum(want) < len(want)
+        if size == 48:
+            d_in = torch.frombuffer(bytearray(b"".join(encs)), dtype=torch.uint8).to(dev)
+            d_aff = torch.zeros(96 * len(encs), dtype=torch.uint8, device=dev)
+            d_ok = torch.zeros(len(encs), dtype=torch.uint8, device=dev)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            assert nat.lib().lcb_g1_to_affine_dev(d_aff.data_ptr(), d_ok.data_ptr(), d_in.data_ptr(), len(encs), st) == 0
+            torch.cuda.synchronize(dev)
+            assert [bool(v) for v in d_ok.cpu().tolist()] == want
+
+
+# ------------------------------------------------------------------ G2.SetHashOf: every entry point, branch by branch
+# The messages of tests/h2g2_cases.py populate every class of (second mask, SvdW candidate, try of the complex root)
+# (asserted on the CPU by tests/test_h2g2_ref.py) and the SHA-512 padding lengths; each entry point below runs its own
+# copy of the hash (lcb_g2_hash_batch: k_scalar.hip; mclBnG2_hashAndMapTo: k_mcl_g2_hash + k_mcl_g2_clear in
+# k_ptmul.hip; lcb_ts_sign and the signature checks: k_ts.hip, k_prep.hip; the TPKE paths: the two-part SHA-512 of
+# U || V in k_scalar.hip, k_tpke.hip and k_prep.hip).
+@pytest.fixture(scope="module")
+def h2g2():
+    import h2g2_cases as C
+    from pyref import bls12_381 as B
+    msgs = [m for m, _ in C.messages()]
+    mapped = [B.map_to_g2_bn((B.fp_hash_of(m), 0)) for m in msgs]
+    return {"C": C, "B": B, "msgs": msgs,
+            "bp": [B.g2_to_bytes(B.clear_cofactor_g2(q)) for q in mapped],
+            "h2": [B.g2_to_bytes(B.g2_mul(q, C.H2)) for q in mapped]}
+
+
+def _cofactor_mode(nat, original):
+    nat.set_original_g2_cofactor(original)
+    o.set_g2_original_cofactor(1 if original else 0)
+
+
+@pytest.mark.parametrize("original", [False, True])
+def test_hash_entry_points_match_oracle_and_model(nat, mcl, h2g2, original):
+    msgs, model = h2g2["msgs"], h2g2["h2" if original else "bp"]
+    one = o.fr(1)
+    try:
+        _cofactor_mode(nat, original)
+        orc = [o.g2_hash(m) for m in msgs]
+        batch = nat.g2_hash_batch(msgs)
+        abi = [mcl.G2().SetHashOf(m).ToBytes() for m in msgs]
+        sigs = nat.ts_sign([one] * len(msgs), msgs, list(range(len(msgs))))        # sk = 1: the signature is H(m)
+        orc_sigs = [o.ts_sign(one, m) for m in msgs]
+        items = [(k, 0, sigs[k]) for k in range(len(msgs))] + [(0, 0, sigs[1])]   # the verification's own hash (k_prep.hip)
+        verified = nat.ts_verify_shares([o.g1_gen()], msgs, items)
+        verified_b = nat.ts_verify_shares([o.g1_gen()], msgs, items, batched=True)
+    finally:
+        _cofactor_mode(nat, False)
+    for k, m in enumerate(msgs):
+        assert orc[k] == model[k], m
+        assert batch[k] == model[k], m
+        assert abi[k] == model[k], m
+        assert sigs[k] == model[k] and orc_sigs[k] == model[k], m
+    assert verified == [True] * len(msgs) + [False] and verified_b == verified
+
+
+@pytest.mark.parametrize("original", [False, True])
+def test_tpke_two_part_hash_matches_oracle_and_model(nat, h2g2, original):
+    """W = [r] H(U || V) with r = 1 and |V| around the SHA-512 block boundaries (48 + |V| = 110 .. 240): the encryption's
+    hash, then the hashes of the share check's and the partial decryption's preparation, which accept the ciphertexts"""
+    C, B = h2g2["C"], h2g2["B"]
+    d = Drbg(b"gpu-h2g2-tpke")
+    x, y, yi, _ = _tpke_setup(d, 4, 1, 0)
+    one = o.fr(1)
+    datas = [d.bytes(n) for n in C.TPKE_V_LENGTHS]
+    try:
+        _cofactor_mode(nat, original)
+        cts = nat.tpke_encrypt_batch(y, [one] * len(datas), datas)
+        orc = [o.tpke_encrypt(y, data, one) for data in datas]
+        shares = [(c, i, o.tpke_decrypt(U, V, W, x[i])) for c, (U, V, W) in enumerate(cts) for i in (0, 3)]
+        exact = nat.tpke_verify_shares(yi, cts, shares)
+        batched = nat.tpke_verify_shares(yi, cts, shares, batched=True)
+        dec = nat.tpke_partial_decrypt(x[1], cts)
+        want_dec = [o.tpke_decrypt(U, V, W, x[1]) for U, V, W in cts]
+    finally:
+        _cofactor_mode(nat, False)
+    for ct, want, data in zip(cts, orc, datas):
+        assert ct == want, len(data)
+        U, V, W = ct
+        assert len(V) == len(data)
+        q = B.map_to_g2_bn((B.fp_hash_of(U + V), 0))
+        h = B.g2_mul(q, C.H2) if original else B.clear_cofactor_g2(q)
+        assert W == B.g2_to_bytes(h), len(data)
+    assert exact == [True] * len(shares) and batched == [True] * len(shares)
+    assert dec == [(True, u) for u in want_dec]

@@ -68,6 +68,7 @@ BUDGET = {
     "k_rlc_search": (106, 4056),              # round 5: baby-step giant-step (fingerprint table + the confirming power)
     "k_secp_scalars": (0, 528),
     "k_secp_debug": (0, 0),                   # test hook: every secp256k1 routine behind one switch (secp_debug.hpp), 171 registers
+    "k_h2g2_debug": (0, 3864),                # test hook: the routines under hash-to-G2 and the point decoders behind one switch (h2g2_debug.hpp), 295 registers
     "k_tpke_ct_prepare": (0, 3800),
     "k_tpke_ct_prepare_h": (5, 4800),
     "k_tpke_ct_prepare_w": (5, 1208),
