@@ -467,6 +467,28 @@ int lcb_debug_h2g2_op(int op, const uint32_t *in, size_t n, uint32_t *out);
 int lcb_debug_tpke_miller(uint32_t *f_out, uint8_t *ok_out, size_t n, const uint8_t *y_keys, size_t n_keys,
                           const uint8_t *cts_u, const uint8_t *cts_w, const uint8_t *v_data, const uint32_t *v_off,
                           size_t n_cts, const uint32_t *ct_idx, const uint32_t *dec_idx, const uint8_t *ui);
+/* The two test hooks of the batched checks' random exponents.  A share's exponent is a + b lambda,
+   lambda = z^2 - 1, with (a, b) words 0 and 1 of the ChaCha20 block (RFC 8439) whose key is the call's 32 getrandom
+   bytes and whose words 12..15 are counter, domain, nonce low, nonce high; (0, 0) reads as (1, 0).  Both return -1
+   unless the environment has LCB_ALLOW_TEST_HOOKS=1: with a secret key they would expose material of the exponents.
+   lcb_debug_rlc_scalars: the device routine that draws (a, b), on n (1..65536) arbitrary items, one lane each.
+   key10[10 i ..] = item i's eight key words and two nonce words, ctr[i] / dom[i] its counter and domain;
+   ab_out[2 i], ab_out[2 i + 1] = its (a, b). */
+int lcb_debug_rlc_scalars(const uint32_t *key10, const uint32_t *ctr, const uint32_t *dom, size_t n, uint32_t *ab_out);
+/* lcb_debug_rlc_records: after a batched TPKE or threshold-signature call on ctx (NULL: the calling thread's implicit
+   context of the *_dev forms), waits for the context's work and returns the two multiples the call's randomisation
+   stored for each of its n shares, as wire bytes (infinity: zero bytes; a share the call left out of its groups, or a
+   share of the census prefix, has two points at infinity).
+   After a TPKE call (*kind = 0): rec_a[48 i ..] = a U_i + b phi(U_i), rec_b[48 i ..] = a Y + b phi(Y) for the share's
+   point U_i and its decryptor's key Y, phi(x, y) = (beta x, y); (a, b) is drawn with counter = the share's bin
+   32 (ct_idx & 3) + (its offset in its run of equal ct_idx) mod 32 and domain 1, or, under
+   lcb_set_rlc_share_exponents(1), counter = i and domain 0.
+   After a threshold-signature call (*kind = 1): rec_a[48 i ..] = a PK + b phi(PK), rec_b[96 i ..] = a S_i + b psi^4(S_i)
+   (96 bytes per share), counter = i, domain 0.
+   *nonce = the call's nonce: the number of batched calls the context has made, this one included.
+   n must equal the last call's share count; -1 otherwise, and when the context has made no batched call. */
+struct lcb_ctx;
+int lcb_debug_rlc_records(struct lcb_ctx *ctx, uint8_t *rec_a, uint8_t *rec_b, size_t n, uint64_t *nonce, int *kind);
 
 /* ------------------------------------------------------------------ explicit execution contexts
    A context owns the device workspaces of the prepare/verify, assembly, Lagrange and MSM calls below

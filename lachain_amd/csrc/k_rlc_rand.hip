@@ -321,7 +321,56 @@ extern "C" __global__ void __launch_bounds__(LCB_BLOCK) __attribute__((amdgpu_wa
     accept[i] = ok;
 }
 
+// ---------------------------------------------------------------- test hooks (lcb_debug_rlc_scalars / _records)
+// rlc_scalar_dom itself on arbitrary (key, nonce, counter, domain) items, one lane each: key10 = 10 words per item (the
+// rlc_key), ab = the two words it returns
+extern "C" __global__ void LCB_BOUNDS k_rlc_scalars_debug(const u32 *key10, const u32 *ctr, const u32 *dom, u32 n,
+                                                         u32 *ab) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    rlc_key key;
+#pragma unroll
+    for (int j = 0; j < 8; j++) key.k[j] = key10[10 * (size_t)i + j];
+    key.nonce[0] = key10[10 * (size_t)i + 8];
+    key.nonce[1] = key10[10 * (size_t)i + 9];
+    u32 a, b;
+    rlc_scalar_dom(key, ctr[i], dom[i], a, b);
+    ab[2 * (size_t)i] = a;
+    ab[2 * (size_t)i + 1] = b;
+}
+// the records the points kernels above stored for shares [i0, n) (quad-major SoA Jacobian), gathered and compressed to
+// wire bytes: outA 48 B per share, outB 48 B (TPKE) or 96 B (ts: G2 records); shares below i0 (the census prefix, never
+// randomised: their slots are not written) and the point at infinity give zero bytes
+extern "C" __global__ void LCB_BOUNDS k_rlc_records_debug(const u32 *rA, const u32 *rB, u32 i0, u32 n, u32 ts,
+                                                         uint8_t *outA, uint8_t *outB) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    g1 p;
+    jac_set_inf(p);
+    if (i >= i0) g1_load_soa(p, rA, n, i);
+    g1_compress_jac(outA + 48 * (size_t)i, p);
+    if (ts) {
+        g2 q;
+        jac_set_inf(q);
+        if (i >= i0) g2_load_soa(q, rB, n, i);
+        g2_compress_jac(outB + 96 * (size_t)i, q);
+    } else {
+        jac_set_inf(p);
+        if (i >= i0) g1_load_soa(p, rB, n, i);
+        g1_compress_jac(outB + 48 * (size_t)i, p);
+    }
+}
+
 // ---------------------------------------------------------------- host launch wrappers
+extern "C" void lcbk_rlc_scalars_debug(hipStream_t s, const u32 *key10, const u32 *ctr, const u32 *dom, u32 n, u32 *ab) {
+    dim3 grid((n + LCB_BLOCK - 1) / LCB_BLOCK);
+    LCB_LAUNCH(k_rlc_scalars_debug, key10, ctr, dom, n, ab);
+}
+extern "C" void lcbk_rlc_records_debug(hipStream_t s, const u32 *rA, const u32 *rB, u32 i0, u32 n, int ts,
+                                       uint8_t *outA, uint8_t *outB) {
+    dim3 grid((n + LCB_BLOCK - 1) / LCB_BLOCK);
+    LCB_LAUNCH(k_rlc_records_debug, rA, rB, i0, n, ts ? 1u : 0u, outA, outB);
+}
 extern "C" void lcbk_ts_rlc_points(hipStream_t s, u32 n_msgs, const void *pks, u32 n_pks, const u32 *msg_idx,
                                    const u32 *pk_idx, const uint8_t *sigs, u32 i0, u32 n, const u32 key[10], u32 *rP,
                                    u32 *rS, uint8_t *accept, void *desc, u32 *count, const u32 *ktab,

@@ -146,6 +146,9 @@ extern "C" void lcbk_rlc_positions(hipStream_t s, const u32 *ct_idx, u32 i0, u32
 extern "C" size_t lcbk_rlc_pos_table_bytes(u32 n_keys);
 extern "C" void lcbk_rlc_pos_table(hipStream_t s, const void *keys, u32 n_keys, const u32 key[10], const u32 *ktab, const uint8_t *ktab_ok, u32 *ws, u32 **P, uint8_t **pinf);
 extern "C" void lcbk_ts_rlc_points(hipStream_t s, u32 n_msgs, const void *pks, u32 n_pks, const u32 *msg_idx, const u32 *pk_idx, const uint8_t *sigs, u32 i0, u32 n, const u32 key[10], u32 *rP, u32 *rS, uint8_t *accept, void *desc, u32 *count, const u32 *ktab, const uint8_t *ktab_ok, const u32 *susp, void *dec);
+// test hooks (lcb_debug_rlc_scalars, lcb_debug_rlc_records): rlc_scalar_dom per item; the points kernels' records of shares [i0, n) as wire bytes
+extern "C" void lcbk_rlc_scalars_debug(hipStream_t s, const u32 *key10, const u32 *ctr, const u32 *dom, u32 n, u32 *ab);
+extern "C" void lcbk_rlc_records_debug(hipStream_t s, const u32 *rA, const u32 *rB, u32 i0, u32 n, int ts, uint8_t *outA, uint8_t *outB);
 extern "C" void lcbk_rlc_groups(hipStream_t s, const u32 *key_idx, u32 i0, u32 n, u32 n_keys, u32 cap, void *desc, u32 *count);
 extern "C" void lcbk_tpke_rlc_sum(dim3 grid, hipStream_t s, const void *desc, u32 n_groups, u32 lanes, const uint8_t *ct_ok, const uint8_t *ct_g2, const void *keys, u32 n_keys, const u32 *dec_idx, const uint8_t *ui, const u32 *rU, const u32 *rY, u32 n, void *gpts, uint8_t *accept, uint8_t *gexact, u32 *wsum, const u32 *susp, uint8_t *cval);
 extern "C" void lcbk_tpke_rlc_wsum(dim3 grid, hipStream_t s, const void *sdesc, u32 n_s, const u32 *wsum, u32 n_l1, void *gpts);

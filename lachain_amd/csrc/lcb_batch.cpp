@@ -147,6 +147,12 @@ bool rlc_key_fill(lcb_ctx *c, u32 key[10]) {
     key[9] = (u32)(c->rlc_calls >> 32);
     return true;
 }
+// what the call's points kernel is about to store in RLC_REC_A / RLC_REC_B (lcb_debug_rlc_records reads it back)
+void rlc_note_records(lcb_ctx *c, int kind, size_t n, size_t m) {
+    c->rlc_last_kind = kind;
+    c->rlc_last_n = n;
+    c->rlc_last_i0 = m < n ? m : n;
+}
 // census size: a prefix of the batch large enough to sample every key a few times (>= 8 shares per key on average,
 // 512 .. 2048 shares), at most a quarter of the batch; 0 = no census (small batches, or disabled)
 u32 census_size(size_t n, size_t n_keys) {
@@ -217,6 +223,7 @@ int rlc_points_enqueue(lcb_ctx *c, RlcWs &w, uint8_t *d_accept, size_t n, size_t
                        const uint32_t *d_ct, const uint32_t *d_dec, const uint8_t *d_ui, hipStream_t s) {
     u32 key[10];
     if (!rlc_key_fill(c, key)) return -1;
+    rlc_note_records(c, RLC_TPKE, n, w.m);
     const bool pos = !g_share_exp.load(), permute = g_lane_perm.load() != 0;
     c->rlc_pos_exp = pos;
     hipEventRecord(c->rlc_ev[0], s);
@@ -251,6 +258,7 @@ int ts_rlc_points_enqueue(lcb_ctx *c, RlcWs &w, uint8_t *d_accept, size_t n, siz
                           const uint8_t *d_sigs, const uint32_t *d_midx, const uint32_t *d_pidx, hipStream_t s) {
     u32 key[10];
     if (!rlc_key_fill(c, key)) return -1;
+    rlc_note_records(c, RLC_TS, n, w.m);
     hipEventRecord(c->rlc_ev[0], s);
     if (w.m < n) {
         uint8_t *kok = w.kok;
@@ -1030,6 +1038,50 @@ extern "C" int lcb_batched_census(uint32_t out[4]) {
 extern "C" int lcb_batched_inflight(int device) {
     if (device < 0 || device >= 64) { set_err("lcb_batched_inflight: device out of range"); return -1; }
     return (int)g_batched_inflight[device].load();
+}
+// ---- test hooks of the batch exponents (LCB_ALLOW_TEST_HOOKS=1: with a secret key they would expose material of it)
+// rlc_scalar_dom (rlc_common.hpp) on n items: key10 = eight key words and two nonce words per item
+extern "C" int lcb_debug_rlc_scalars(const uint32_t *key10, const uint32_t *ctr, const uint32_t *dom, size_t n,
+                                     uint32_t *ab_out) {
+    if (!env_on("LCB_ALLOW_TEST_HOOKS")) { set_err("lcb_debug_rlc_scalars: needs LCB_ALLOW_TEST_HOOKS=1"); return -1; }
+    if (!n || n > 65536 || !key10 || !ctr || !dom || !ab_out) { set_err("lcb_debug_rlc_scalars: 1..65536 items"); return -1; }
+    SYNC_CTX_OR(c, -1)
+    HostCall h(c, "lcb_debug_rlc_scalars");
+    const u32 *dk = h.in(key10, 10 * n), *dc = h.in(ctr, n), *dd = h.in(dom, n);
+    u32 *dab = h.out<u32>(2 * n);
+    if (!h.ok()) return -1;
+    lcbk_rlc_scalars_debug(h.s, dk, dc, dd, (u32)n, dab);
+    h.back(ab_out, dab, 8 * n);
+    return h.finish();
+}
+// the records the last batched call of the context stored per share (RLC_REC_A, RLC_REC_B), as wire bytes, with the
+// call's nonce and kind.  The levels only read the records, so they are what the group sums were formed from.
+extern "C" int lcb_debug_rlc_records(lcb_ctx *ctx, uint8_t *rec_a, uint8_t *rec_b, size_t n, uint64_t *nonce, int *kind) {
+    if (!env_on("LCB_ALLOW_TEST_HOOKS")) { set_err("lcb_debug_rlc_records: needs LCB_ALLOW_TEST_HOOKS=1"); return -1; }
+    CTX_OR(c, ctx, -1)
+    HostCall h(c, "lcb_debug_rlc_records");      // ordered behind the context's work; finish() waits for it
+    if (c->rlc_last_kind < 0) { set_err("lcb_debug_rlc_records: no batched call has run in this context"); return -1; }
+    if (!n || n != c->rlc_last_n || !rec_a || !rec_b) {
+        set_err("lcb_debug_rlc_records: n is not the last batched call's share count");
+        return -1;
+    }
+    const bool ts = c->rlc_last_kind == RLC_TS;
+    const size_t wb = ts ? 96 : 48;
+    const u32 *rA = (const u32 *)c->rlc[RLC_REC_A].p, *rB = (const u32 *)c->rlc[RLC_REC_B].p;
+    if (!rA || !rB || c->rlc[RLC_REC_A].cap < n * LCB_G1_JAC_BYTES ||
+        c->rlc[RLC_REC_B].cap < n * (ts ? LCB_G2_JAC_BYTES : LCB_G1_JAC_BYTES)) {
+        set_err("lcb_debug_rlc_records: the context holds no records");
+        return -1;
+    }
+    uint8_t *da = h.out<uint8_t>(48 * n), *db = h.out<uint8_t>(wb * n);
+    if (!h.ok()) return -1;
+    lcbk_rlc_records_debug(h.s, rA, rB, (u32)c->rlc_last_i0, (u32)n, ts ? 1 : 0, da, db);
+    h.back(rec_a, da, 48 * n);
+    h.back(rec_b, db, wb * n);
+    if (h.finish()) return -1;
+    if (nonce) *nonce = c->rlc_calls;
+    if (kind) *kind = c->rlc_last_kind;
+    return 0;
 }
 // ---- knobs
 extern "C" void lcb_set_batch_seed(const uint8_t *seed32) {

@@ -267,6 +267,10 @@ struct lcb_ctx {
     uint32_t rlc_census[CENSUS_N] = {};
     int rlc_nlev = 0;
     uint64_t rlc_calls = 0;
+    // what the last batched call's randomisation wrote into rlc[RLC_REC_A / RLC_REC_B], for lcb_debug_rlc_records (test
+    // hook): its shares, its census prefix (shares [0, i0) have no records) and its kind (-1: none yet, 0 TPKE, 1 TS)
+    size_t rlc_last_n = 0, rlc_last_i0 = 0;
+    int rlc_last_kind = -1;
     // which prepared line sets are not normalised (adversarial W): [0] the census's ciphertexts, [1] all; the one-lane
     // Miller fallback is dispatched only when the flag is set (round 5: an idle fallback dispatch waited ~15 ms for a
     // SIMD with 360 free registers behind the randomisation).  Device words, pinned copies, events after the copies.

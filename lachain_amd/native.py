@@ -126,6 +126,10 @@ _SIGS = {
                                          ctypes.POINTER(ctypes.c_uint32)]),
     "lcb_debug_tpke_miller": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32), c_u8p, c_size, c_u8p, c_size, c_u8p, c_u8p,
                                              c_u8p, c_u32p, c_size, c_u32p, c_u32p, c_u8p]),
+    "lcb_debug_rlc_scalars": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_size,
+                                             ctypes.c_void_p]),
+    "lcb_debug_rlc_records": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_size,
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
     "lcb_batched_census": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32)]),
     "lcb_tpke_partial_decrypt": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u32p, c_size]),
     "lcb_tpke_encrypt_phase1": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, c_size]),
@@ -1622,6 +1626,40 @@ def debug_tpke_miller(y_keys, cts, shares):
     _check(lib().lcb_debug_tpke_miller(f, po, n, py, len(y_keys), pu, pw, pv, pvo, len(cts), pct, pdec, pui),
            "debug_tpke_miller")
     return [(list(f[144 * i:144 * i + 144]), bool(ob[i])) for i in range(n)]
+
+
+def debug_rlc_scalars(items):
+    """test hook (LCB_ALLOW_TEST_HOOKS=1): the device routine that draws the batch exponents' words, on items
+    (key32 bytes, nonce, counter, domain) -> [(a, b)] (lcb_debug_rlc_scalars)"""
+    import numpy as np
+    n = len(items)
+    key10 = np.zeros((n, 10), dtype=np.uint32)
+    for i, (key32, nonce, _, _) in enumerate(items):
+        key10[i, :8] = np.frombuffer(key32, dtype="<u4")
+        key10[i, 8] = nonce & 0xFFFFFFFF
+        key10[i, 9] = nonce >> 32
+    ctr = np.array([it[2] for it in items], dtype=np.uint32)
+    dom = np.array([it[3] for it in items], dtype=np.uint32)
+    ab = np.zeros((n, 2), dtype=np.uint32)
+    _check(lib().lcb_debug_rlc_scalars(key10.ctypes.data, ctr.ctypes.data, dom.ctypes.data, n, ab.ctypes.data),
+           "debug_rlc_scalars")
+    return [(int(a), int(b)) for a, b in ab]
+
+
+def debug_rlc_records(n, ctx=None):
+    """test hook (LCB_ALLOW_TEST_HOOKS=1): what the randomisation of the last batched call of ctx (None: this thread's
+    implicit context of the *_dev forms) stored for its n shares -> (rec_a, rec_b, nonce, kind): two lists of wire
+    points (48 bytes; rec_b 96 bytes when kind = 1, threshold signatures), the call's nonce, 0 for TPKE
+    (lcb_debug_rlc_records)"""
+    ra = ctypes.create_string_buffer(48 * max(1, n))
+    rb = ctypes.create_string_buffer(96 * max(1, n))
+    nonce = ctypes.c_uint64()
+    kind = ctypes.c_int(-1)
+    _check(lib().lcb_debug_rlc_records(None if ctx is None else ctx.ptr, ra, rb, n, ctypes.byref(nonce),
+                                       ctypes.byref(kind)), "debug_rlc_records")
+    w = 96 if kind.value == 1 else 48
+    return ([ra.raw[48 * i:48 * i + 48] for i in range(n)], [rb.raw[w * i:w * i + w] for i in range(n)],
+            int(nonce.value), int(kind.value))
 
 
 def batched_census():
