@@ -276,11 +276,13 @@ int lcb_set_keys_first(int on);
    lcb_set_rlc_lane_permutation(0): the randomisation's lanes take the shares in batch order; 1 (default): sorted by
    exponent, so that a wave skips the ladder columns its one exponent does not need.  lcb_set_rlc_pos_table_min: with
    position exponents, batches of at least this many shares per key read the keys' multiples from a table of 128 per key
-   (default 512; 0: always; UINT32_MAX: never).  The decisions are the same in every setting.  Tuning hooks: -1 unless
-   LCB_ALLOW_TUNING=1. */
+   (default 512; 0: always; UINT32_MAX: never).  lcb_set_rlc_signed_digits(1) (default): a wave that holds one exponent
+   walks its Joint Sparse Form (signed digits, about 16.5 additions instead of 24); 0: its binary columns.  The exponents
+   and the decisions are the same in every setting.  Tuning hooks: -1 unless LCB_ALLOW_TUNING=1. */
 int lcb_set_rlc_share_exponents(int on);
 int lcb_set_rlc_lane_permutation(int on);
 int lcb_set_rlc_pos_table_min(uint32_t shares_per_key);
+int lcb_set_rlc_signed_digits(int on);
 
 /* Randomized batch form of lcb_tpke_verify_prepared_dev (same arguments, same workspace, same validity rules;
    replaces the per-share loop over TPKE/PublicKey.cs:88-92 driven from HoneyBadger.cs:211-212).  Shares are grouped

@@ -73,13 +73,14 @@ extern "C" __global__ void LCB_BOUNDS k_rlc_key_tables(const g1a_st *keys, u32 n
 // exponent and g1_mul_ab_wave skips the columns it does not need as a wave), or share i0 + t without perm.  bin: the
 // share's exponent is the bin's, t[bin] (position exponents); without it the share's own, from its index.  P / pinf
 // (with bin only): the share's Y record is P[bin][d] (k_rlc_pos_table).  Every record is stored at the share's index.
+// jsf: a wave of one exponent walks its signed joint-sparse digits (g1_mul_ab_jsf), its parked addend in the rU record.
 extern "C" __global__ void __launch_bounds__(LCB_BLOCK) __attribute__((amdgpu_waves_per_eu(1)))
 k_tpke_rlc_points(u32 n_cts, const g1a_st *keys, u32 n_keys, const u32 *ct_idx,
                                                        const u32 *dec_idx, const uint8_t *ui, u32 i0, u32 n,
                                                        rlc_key key, u32 *rU, u32 *rY, uint8_t *accept,
                                                        const u32 *ktab, const uint8_t *ktab_ok, const u32 *susp,
                                                        const u32 *perm, const uint8_t *bin, const u32 *P,
-                                                       const uint8_t *pinf) {
+                                                       const uint8_t *pinf, u32 jsf) {
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n - i0) return;
     u32 i = perm ? perm[t] : i0 + t;
@@ -101,7 +102,7 @@ k_tpke_rlc_points(u32 n_cts, const g1a_st *keys, u32 n_keys, const u32 *ct_idx,
         // share side's point is then not live across the key side's call (its 36 words were the kernel's spills)
         {
             g1 p;
-            g1_mul_ab_wave(p, Ui, a, b);
+            g1_mul_ab_wave(p, Ui, a, b, jsf != 0, rU, n, i);      // (its parked addend in the record stored next)
             g1_store_soa(rU, n, i, p);
         }
         g1 q;
@@ -398,14 +399,14 @@ extern "C" void lcbk_tpke_rlc_points(hipStream_t s, u32 n_cts, const void *keys,
                                      const u32 *dec_idx, const uint8_t *ui, u32 i0, u32 n, const u32 key[10], u32 *rU,
                                      u32 *rY, uint8_t *accept, const u32 *ktab, const uint8_t *ktab_ok,
                                      const u32 *susp, const u32 *perm, const uint8_t *bin, const u32 *P,
-                                     const uint8_t *pinf) {
+                                     const uint8_t *pinf, int signed_digits) {
     rlc_key k;
     for (int j = 0; j < 8; j++) k.k[j] = key[j];
     k.nonce[0] = key[8];
     k.nonce[1] = key[9];
     dim3 grid((n - i0 + LCB_BLOCK - 1) / LCB_BLOCK);
     LCB_LAUNCH(k_tpke_rlc_points, n_cts, (const g1a_st *)keys, n_keys, ct_idx, dec_idx, ui, i0, n, k, rU, rY, accept,
-               ktab, ktab_ok, susp, perm, bin, bin ? P : nullptr, pinf);
+               ktab, ktab_ok, susp, perm, bin, bin ? P : nullptr, pinf, signed_digits ? 1u : 0u);
 }
 extern "C" void lcbk_tpke_rlc_sum(dim3 grid, hipStream_t s, const void *desc, u32 n_groups, u32 lanes,
                                   const uint8_t *ct_ok, const uint8_t *ct_g2, const void *keys, u32 n_keys,

@@ -140,7 +140,7 @@ extern "C" void lcbk_gcm_encrypt(hipStream_t s, const uint8_t *keys32, const uin
 extern "C" void lcbk_gcm_decrypt(hipStream_t s, const uint8_t *keys32, const uint8_t *ct, const uint64_t *ct_off, const uint64_t *out_off, u32 n, u32 hdr, uint8_t *pt_out, uint8_t *ok_out, const uint8_t *ok_in);
 extern "C" size_t lcbk_key_table_bytes(u32 n_keys);
 extern "C" void lcbk_rlc_key_tables(dim3 grid, hipStream_t s, const void *keys, u32 n_keys, u32 *ws, u32 **tab, uint8_t **ktab_ok);
-extern "C" void lcbk_tpke_rlc_points(hipStream_t s, u32 n_cts, const void *keys, u32 n_keys, const u32 *ct_idx, const u32 *dec_idx, const uint8_t *ui, u32 i0, u32 n, const u32 key[10], u32 *rU, u32 *rY, uint8_t *accept, const u32 *ktab, const uint8_t *ktab_ok, const u32 *susp, const u32 *perm, const uint8_t *bin, const u32 *P, const uint8_t *pinf);
+extern "C" void lcbk_tpke_rlc_points(hipStream_t s, u32 n_cts, const void *keys, u32 n_keys, const u32 *ct_idx, const u32 *dec_idx, const uint8_t *ui, u32 i0, u32 n, const u32 key[10], u32 *rU, u32 *rY, uint8_t *accept, const u32 *ktab, const uint8_t *ktab_ok, const u32 *susp, const u32 *perm, const uint8_t *bin, const u32 *P, const uint8_t *pinf, int signed_digits);
 extern "C" size_t lcbk_rlc_pos_bins_bytes(void);
 extern "C" void lcbk_rlc_positions(hipStream_t s, const u32 *ct_idx, u32 i0, u32 n, u32 n_cts, uint8_t *bin, u32 *bins, u32 *perm);
 extern "C" size_t lcbk_rlc_pos_table_bytes(u32 n_keys);

@@ -201,7 +201,7 @@ u32 *rlc_key_tables(lcb_ctx *c, const void *keys, size_t n_keys, hipStream_t s, 
 // its index (the form before the position exponents); 0 (default): per group position, t[set][pos].
 // lcb_set_rlc_lane_permutation(0): lane t of the randomisation handles share m + t; 1 (default): the shares sorted by
 // bin, so that a wave holds one exponent and skips its zero columns as a wave.  Each half can be measured alone.
-// (LCB_RLC_SHARE_EXP, LCB_RLC_LANE_PERM and LCB_RLC_POS_TABLE_MIN, with LCB_ALLOW_TUNING=1, set the starting values: A/B
+// (LCB_RLC_SHARE_EXP, LCB_RLC_LANE_PERM, LCB_RLC_SIGNED_DIGITS and LCB_RLC_POS_TABLE_MIN, with LCB_ALLOW_TUNING=1, set the starting values: A/B
 // runs of programs that do not call the setters)
 long tuning_env(const char *name, long dflt) {
     const char *e = getenv(name);
@@ -209,6 +209,10 @@ long tuning_env(const char *name, long dflt) {
 }
 std::atomic<int> g_share_exp{tuning_env("LCB_RLC_SHARE_EXP", 0) ? 1 : 0};
 std::atomic<int> g_lane_perm{tuning_env("LCB_RLC_LANE_PERM", 1) ? 1 : 0};
+// lcb_set_rlc_signed_digits(1) (default; LCB_RLC_SIGNED_DIGITS): a wave of the randomisation that holds one exponent
+// walks its Joint Sparse Form, ~16.5 additions instead of ~24 (rlc_common.hpp g1_mul_ab_jsf); 0: the binary columns.
+// The exponents, the records' points and the decisions are the same either way.
+std::atomic<int> g_signed_digits{tuning_env("LCB_RLC_SIGNED_DIGITS", 1) ? 1 : 0};
 // P = t[bin] Y_d for 128 bins x n_keys keys replaces the key side's eight table additions per share: an entry costs
 // about 200 Fp products (eight mixed additions and one inversion), 25,600 per key; a share saves about 88, so the
 // table repays itself from 291 shares per key.  512 leaves room for the table's latency ahead of the randomisation
@@ -247,7 +251,7 @@ int rlc_points_enqueue(lcb_ctx *c, RlcWs &w, uint8_t *d_accept, size_t n, size_t
             lcbk_rlc_pos_table(s, c->t_keys.p, (u32)n_keys, key, ktab, kok, pws, &P, &pinf);
         }
         lcbk_tpke_rlc_points(s, (u32)n_cts, c->t_keys.p, (u32)n_keys, d_ct, d_dec, d_ui, w.m, (u32)n, key, w.rA, w.rB,
-                             d_accept, ktab, kok, w.susp, perm, pos ? bin : nullptr, P, pinf);
+                             d_accept, ktab, kok, w.susp, perm, pos ? bin : nullptr, P, pinf, g_signed_digits.load());
         static_assert(LCB_RLC_GROUP_CAP == 32, "the position bins hold the level-1 groups' cap (rlc_common.hpp RLC_POS_CAP)");
         lcbk_rlc_groups(s, d_ct, w.m, (u32)n, (u32)n_cts, LCB_RLC_GROUP_CAP, w.dA, w.cnt + CNT_GROUPS);
     }
@@ -1133,6 +1137,11 @@ extern "C" int lcb_set_rlc_share_exponents(int on) {
 extern "C" int lcb_set_rlc_lane_permutation(int on) {
     if (!tuning_allowed("lcb_set_rlc_lane_permutation")) return -1;
     g_lane_perm.store(on ? 1 : 0);
+    return 0;
+}
+extern "C" int lcb_set_rlc_signed_digits(int on) {
+    if (!tuning_allowed("lcb_set_rlc_signed_digits")) return -1;
+    g_signed_digits.store(on ? 1 : 0);
     return 0;
 }
 extern "C" int lcb_set_rlc_pos_table_min(uint32_t shares_per_key) {

@@ -4,6 +4,7 @@
 // fixed-base tables.
 #pragma once
 #include "kcommon.hpp"
+#include "rlc_jsf.hpp"
 
 struct rlc_key { u32 k[8]; u32 nonce[2]; };   // ChaCha20 key (256 bit, from getrandom) and a per-call nonce
 
@@ -172,11 +173,86 @@ DI void g1_mul_ab_inl(g1 &r, const g1a &P, u32 a, u32 b) {
 // first, the exponent is taken from that lane: it is wave-uniform (scalar registers), so a column with a = b = 0 is
 // skipped by a scalar branch and the wave issues the ~24 additions its exponent needs instead of 32.  A mixed wave
 // takes the per-lane ladder; both give the same point.
-DI void g1_mul_ab_wave(g1 &r, const g1a &P, u32 a, u32 b) {
+//
+// Signed digits (jsf, lcb_set_rlc_signed_digits, default): the uniform exponent is recoded to its Joint Sparse Form
+// (rlc_jsf.hpp: 33 columns of digits in {-1, 0, 1}, half of them zero in both rows) and the wave issues ~16.5 additions.
+// The addends are +-P, +-phi(P), +-(P + phi(P)) and +-(P - phi(P)); the last is the one addend with no free affine form
+// (1 - phi has norm 3), so the ladder runs on the isomorphic curve y^2 = x^3 + 4 h^6, (x, y) -> (h^2 x, h^3 y) with
+// h = (beta - 1) x: the chord through P and -phi(P) has slope -2y / h, so D = P - phi(P) is (X : Y : h) in Jacobian
+// coordinates, i.e. affine (X, Y) over there,
+//     X = 4 y^2 - (x' + beta x'),  Y = 2 y (X - x') - y',  x' = h^2 x,  y' = h^3 y
+// (x + beta x + beta^2 x = 0).  The doubling and the mixed addition (a = 0) do not read the curve's constant, phi is
+// (x, y) -> (beta x, y) on both curves, and a result (X3 : Y3 : Z3) over there is (X3 : Y3 : h Z3) here.  Cost: 8
+// products ahead of the ladder and one after it.  D and h are parked in the share's output record rec (36 words,
+// overwritten with the result by the caller) and read back where a column needs them: x', y' and beta x' are what
+// stays live, as x, y and beta x do in the binary form.  A lane with x = 0 (the points of order 3: phi(P) = P, h = 0)
+// sends its wave to the binary ladder.
+DI void g1_mul_ab_jsf(g1 &r, const g1a &P, u32 a, u32 b, u32 *rec, size_t n, size_t i) {
+    rlc_jsf j;
+    rlc_jsf_recode(j, a, b);
+    const u64 nz = j.nz_a | j.nz_b;
+    jac_set_inf(r);
+    if (!nz) return;
+    fp x, y, bx;                                 // P on the scaled curve, and beta x'
+    {
+        fp beta, t;
+        g1 st;                                   // st.x, st.y: D; st.z: h
+        fp_load_const(beta, LCB_G1_BETA);
+        fp_mul(bx, P.x, beta);
+        fp_sub(st.z, bx, P.x);                   // h = (beta - 1) x
+        fp_sqr(t, st.z);
+        fp_mul(x, P.x, t);                       // x' = h^2 x
+        fp_mul(t, t, st.z);
+        fp_mul(y, P.y, t);                       // y' = h^3 y
+        fp_mul(bx, x, beta);
+        fp_sqr(t, P.y);
+        fp_add(t, t, t);
+        fp_add(t, t, t);
+        fp_add(st.x, x, bx);
+        fp_sub(st.x, t, st.x);                   // X = 4 y^2 - (x' + beta x')
+        fp_sub(t, st.x, x);
+        fp_mul(t, t, P.y);
+        fp_add(t, t, t);
+        fp_sub(st.y, t, y);                      // Y = 2 y (X - x') - y'
+        g1_store_soa(rec, n, i, st);
+    }
+    const int top = 63 - __builtin_clzll(nz);
+#pragma unroll 1
+    for (int k = top; k >= 0; k--) {
+        if (k != top) jac_dbl(r, r);
+        if (!((nz >> k) & 1)) continue;
+        const bool da = (j.nz_a >> k) & 1, db = (j.nz_b >> k) & 1, sa = (j.neg_a >> k) & 1, sb = (j.neg_b >> k) & 1;
+        fp ax, ay;
+        bool neg;
+        if (da && db && sa != sb) {              // +-(P - phi(P))
+            asm volatile("" ::: "memory");
+            soa_load<12>(&ax, rec, n, i);
+            soa_load<12>(&ay, rec + (size_t)12 * n, n, i);
+            neg = sa;
+        } else if (da && db) {                   // +-(P + phi(P)), P + phi(P) = (beta^2 x, -y)
+            fp_add(ax, x, bx);
+            fp_neg(ax, ax);
+            ay = y;
+            neg = !sa;
+        } else {
+            ax = da ? x : bx;
+            ay = y;
+            neg = da ? sa : sb;
+        }
+        if (neg) fp_neg(ay, ay);
+        jac_add_aff(r, r, ax, ay);
+    }
+    fp h;
+    asm volatile("" ::: "memory");
+    soa_load<12>(&h, rec + (size_t)24 * n, n, i);
+    fp_mul(r.z, r.z, h);
+}
+DI void g1_mul_ab_wave(g1 &r, const g1a &P, u32 a, u32 b, bool jsf, u32 *rec, size_t n, size_t i) {
     if (P.inf) { jac_set_inf(r); return; }       // (leaves the ballot to the lanes that run a ladder)
     const u32 a0 = (u32)__builtin_amdgcn_readfirstlane((int)a), b0 = (u32)__builtin_amdgcn_readfirstlane((int)b);
-    if (__ballot(a != a0 || b != b0) == 0) g1_mul_ab_inl(r, P, a0, b0);
-    else g1_mul_ab_inl(r, P, a, b);
+    if (__ballot(a != a0 || b != b0) != 0) g1_mul_ab_inl(r, P, a, b);
+    else if (!jsf || __ballot(fp_is_zero(P.x)) != 0) g1_mul_ab_inl(r, P, a0, b0);
+    else g1_mul_ab_jsf(r, P, a0, b0, rec, n, i);
 }
 // G2 form of g1_mul_ab_inl: a S + b psi^4(S) with the point arithmetic inlined; lean form: x, y and beta x live, the
 // psi^4 addend's beta^2 x = -(x + beta x) and the joint addend psi^2(S) = (beta x, -y) formed per column

@@ -67,6 +67,7 @@ _SIGS = {
     "lcb_set_rlc_share_exponents": (ctypes.c_int, [ctypes.c_int]),
     "lcb_set_rlc_lane_permutation": (ctypes.c_int, [ctypes.c_int]),
     "lcb_set_rlc_pos_table_min": (ctypes.c_int, [ctypes.c_uint32]),
+    "lcb_set_rlc_signed_digits": (ctypes.c_int, [ctypes.c_int]),
     "lcb_test_linesets": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t,
                                           ctypes.c_void_p, ctypes.c_void_p]),
     "lcb_tpke_verify_shares": (ctypes.c_int, [c_u8p, c_size, c_u8p, c_size, c_u8p, c_u8p, c_u8p, c_u32p, c_size,
@@ -1418,6 +1419,11 @@ def set_rlc_lane_permutation(on):
 def set_rlc_pos_table_min(shares_per_key):
     """batched TPKE check: the keys' per-position table from this many shares per key (default 512; 0: always)"""
     _tuning(lib().lcb_set_rlc_pos_table_min(int(shares_per_key)), "set_rlc_pos_table_min")
+
+
+def set_rlc_signed_digits(on):
+    """batched TPKE check: wave-uniform ladders on the exponent's Joint Sparse Form (default on)"""
+    _tuning(lib().lcb_set_rlc_signed_digits(1 if on else 0), "set_rlc_signed_digits")
 
 
 def set_wave_priority(on):
